@@ -6,9 +6,16 @@ synthetic store resident in HBM (BASELINE.json configs[1]).  value =
 whole-job queries/sec.  N>1: launched by torch.distributed.run, one rank
 per GPU, store partitioned by vid % N, per-step RCCL all-to-allv.
 
-Env knobs: WK_UNIV (default 2560), WK_CPU_UNIV (cpu_baseline sample,
-default = the workload scale: SAME inputs), WK_SKIP_CPU_BASELINE=1,
-WK_SKIP_GATES=1, WK_EMU_EMBED (embedded emulator queries, 0 = off),
+A plain run sets up, warms up, times the K steps and prints the result
+line.  --full adds the diagnostic legs (self-parity gates, per-query
+latency pass, run-to-run spread, roofline probe, embedded emulator
+leg, cpu_baseline); --dump-outputs DIR writes what the last timed step
+left behind as DIR/<name>.npy (see dump_outputs).
+
+Env knobs: WK_UNIV (default 2560), and under --full WK_CPU_UNIV
+(cpu_baseline sample, default = the workload scale: SAME inputs),
+WK_SKIP_CPU_BASELINE=1, WK_SKIP_GATES=1, WK_EMU_EMBED (embedded
+emulator queries, 0 = off);
 WK_DIST_BACKEND=gloo (single-GPU rehearsal of the N>1 path); the full
 knob table (WK_INFLIGHT, WK_GRAPH, WK_FN/CSR/TBM budgets, ...) is in
 README.md.
@@ -29,12 +36,70 @@ os.environ.setdefault("WK_KERNEL_TIMING", "1")
 HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md)
 
 
+T_START = time.time()
+
+
 def log(*a):
-    print(*a, file=sys.stderr, flush=True)
+    print(f"[{time.time() - T_START:6.1f}s]", *a, file=sys.stderr, flush=True)
 
 
 def pctl(xs, p):
     return float(np.percentile(np.asarray(xs), p)) if xs else None
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 20160101
+
+
+def canonical_table(tbl, budget_bytes):
+    """Result tables are multisets (row order depends on atomics), so
+    the dumped form is the lexicographically sorted table, as float64
+    (u32 ids are exact).  A table over its byte budget is cut to a
+    fixed, seeded row sample of the sorted table."""
+    a = np.asarray(tbl)
+    if a.ndim != 2 or a.size == 0:
+        return np.zeros((0, a.shape[1] if a.ndim == 2 else 0), np.float64)
+    a = a[np.lexsort(a.T[::-1])]
+    max_rows = max(1, budget_bytes // (8 * a.shape[1]))
+    if a.shape[0] > max_rows:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        a = a[np.sort(rng.choice(a.shape[0], size=max_rows, replace=False))]
+    return a.astype(np.float64)
+
+
+def dump_outputs(outdir, names, last_table, last_rows, replay):
+    """--dump-outputs: the arrays a caller of the timed path can get.
+
+    last_step_<q>_table / last_step_<q>_rows: the final query's device
+    table and blind row count exactly as the LAST timed step left them
+    (each query of a pass reuses the engine's table buffers, so only
+    the pass's final query survives the step).  <q>_table / row_counts:
+    one extra untimed pass over the same prepared queries (the captured
+    graphs where the timed loop replayed graphs), fetched query by
+    query.  Tables are canonicalised by canonical_table(); a query with
+    no result rows gets no table file (its zero stands in the counts)."""
+    os.makedirs(outdir, exist_ok=True)
+    per_table = DUMP_BUDGET_BYTES // (len(names) + 2)
+    arrays = {}
+    if last_table is not None and last_table.size:
+        arrays[f"last_step_{names[-1]}_table"] = canonical_table(
+            last_table, per_table)
+    if last_rows is not None:
+        arrays[f"last_step_{names[-1]}_rows"] = np.array(
+            [last_rows], dtype=np.float64)
+    counts = []
+    for name in names:
+        nrows, tbl = replay(name)
+        counts.append(nrows)
+        if tbl is not None and tbl.size:
+            arrays[f"{name}_table"] = canonical_table(tbl, per_table)
+    arrays["row_counts"] = np.array(counts, dtype=np.float64)
+    total = 0
+    for key, arr in arrays.items():
+        np.save(os.path.join(outdir, key + ".npy"), arr)
+        total += arr.nbytes
+    assert total <= DUMP_BUDGET_BYTES, total
+    log(f"[dump] {len(arrays)} arrays, {total / 1e6:.1f} MB -> {outdir}")
 
 
 def cpu_baseline(nuniv_workload, seed, triples=None):
@@ -390,9 +455,21 @@ def main():
                     help="emulator light-mix mode: run N template queries "
                          "(A1-A6, mix_config weights) through the in-flight "
                          "window; reports its own JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the diagnostic legs: self-parity gates, "
+                         "per-query latency pass, run-to-run spread, roofline "
+                         "probe, embedded emulator leg, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args()
 
-    import torch
+    # no benchmark plan (LUBM Q1-Q7, emulator A1-A6, WatDiv templates)
+    # has a predicate variable, so the per-vertex predicate lists that
+    # only such plans read are not built or uploaded (WK_VERSATILE=1
+    # brings them back)
+    os.environ.setdefault("WK_VERSATILE", "0")
+
     import wukong_amd as wk
     from wukong_amd import queries as Q
 
@@ -412,6 +489,7 @@ def main():
         dataset = f"WatDiv-{args.watdiv}p"
 
     if distributed:
+        import torch
         import torch.distributed as dist
         # WK_DIST_BACKEND=gloo: single-GPU rehearsal of the full N>1
         # code path (host exchanges; RCCL refuses 2 ranks on 1 device)
@@ -431,7 +509,7 @@ def main():
     store = wk.Store(triples, sid=rank, nsrv=world)
     # the cpu_baseline leg reuses the SAME generated inputs (north_star:
     # reference CPU engine timed on the same inputs)
-    keep_triples = (not distributed and not args.watdiv
+    keep_triples = (args.full and not distributed and not args.watdiv
                     and os.environ.get("WK_SKIP_CPU_BASELINE") != "1"
                     and int(os.environ.get("WK_CPU_UNIV", str(nuniv))) == nuniv)
     if not keep_triples:
@@ -551,11 +629,22 @@ def main():
         while pending:
             drain_one()
 
+    def device_sync():
+        # whole-device sync on this rank's GPU, straight from the HIP
+        # runtime the engine library links (a single-GPU run never
+        # needs torch, whose import and context cost seconds of setup)
+        if distributed:
+            torch.cuda.synchronize(local_rank)
+            return
+        hip = wk._lib
+        if hip.hipSetDevice(local_rank) or hip.hipDeviceSynchronize():
+            raise RuntimeError("hipDeviceSynchronize failed")
+
     def sync():
-        torch.cuda.synchronize(local_rank)
+        device_sync()
         if distributed:
             dist.barrier()
-            torch.cuda.synchronize(local_rank)
+            device_sync()
 
     def all_stats():
         tot = {}
@@ -568,6 +657,7 @@ def main():
         return tot
 
     # warmup
+    log(f"[rank {rank}] warmup...")
     if distributed or inflight == 1:
         run_suite(passes=args.warmup)
         build_graphs()
@@ -579,9 +669,10 @@ def main():
     # at-scale self-parity gates (the gsck idea, gchecker.hpp:364-392):
     # store integrity scan + per-query counts must agree between the
     # functional-map and classic dispatch paths AND between graph replay
-    # and submit — asserted on the full workload store every bench run
+    # and submit — asserted on the full workload store (--full runs)
     gates = None
-    if not distributed and os.environ.get("WK_SKIP_GATES") != "1":
+    if (args.full and not distributed
+            and os.environ.get("WK_SKIP_GATES") != "1"):
         t0 = time.time()
         viol = store.check()
         if viol:
@@ -614,20 +705,23 @@ def main():
 
     lat = {}
     # full graph coverage: per-query latencies from a dedicated
-    # sequential pass, then the TIMED loop enqueues all replays of a
-    # pass back-to-back with ONE sync (the reference proxy's in-flight
-    # window applied to replays; graphs serialize safely on one stream)
+    # sequential pass (--full), then the TIMED loop enqueues all replays
+    # of a pass back-to-back with ONE sync (the reference proxy's
+    # in-flight window applied to replays; graphs serialize safely on
+    # one stream)
     graphs_all = (not distributed and inflight == 1
                   and all(n in graph_ids for n in names))
     suite_gid = None
     if graphs_all:
-        run_suite(collect=lat, passes=3)
+        if args.full:
+            run_suite(collect=lat, passes=3)
         try:
             # whole-pass capture: ONE instantiated graph for all 7
             # queries -> the graph-replay floor is paid once per pass
             suite_gid = eng.graph_build_suite([Q_ALL[n] for n in names])
         except Exception as ex:
             log(f"[graph] suite capture fallback ({ex})")
+    log(f"[rank {rank}] timed region: {args.steps} steps...")
     t_start = time.time()
     if graphs_all:
         try:
@@ -651,10 +745,32 @@ def main():
     elapsed = time.time() - t_start
     stats1 = all_stats()
 
+    if args.dump_outputs and rank == 0:
+        single = not distributed and inflight == 1
+        # the single-engine loops leave the pass's final query resident
+        last_table = eng.fetch_raw() if single else None
+        last_rows = (last_table.shape[0] if single
+                     else lat.get("_rows", {}).get(names[-1]))
+
+        def replay(name):
+            if not single:  # counts of the last timed pass; no tables
+                return lat.get("_rows", {}).get(name, -1), None
+            nrows = None
+            if name in graph_ids:
+                try:
+                    nrows = eng.graph_run(graph_ids[name])
+                except OverflowError:
+                    pass
+            if nrows is None:
+                nrows = eng.run_query_count(Q_ALL[name])
+            return nrows, eng.fetch_raw()
+
+        dump_outputs(args.dump_outputs, names, last_table, last_rows, replay)
+
     # run-to-run spread: repeat the identical timed region (diagnostic
     # only — `value` comes from the official K-step region above)
     spread = None
-    if graphs_all and elapsed < 5.0:
+    if args.full and graphs_all and elapsed < 5.0:
         reps = [elapsed]
         for _ in range(2):
             t0 = time.time()
@@ -688,7 +804,7 @@ def main():
     # workload's largest single step (Q1's 6.4M-row known_to_unknown):
     # algorithmic bytes (device-counted) / HIP-event launch time
     def roofline_probe():
-        if distributed:
+        if distributed or not args.full:
             return {}, {}, {}, {}
         if args.watdiv:
             return {}, {}, {}, {}
@@ -784,7 +900,7 @@ def main():
     # reported inside THIS json line.  WK_EMU_EMBED=0 disables.
     emu_rec = None
     n_emu = int(os.environ.get("WK_EMU_EMBED", "200000"))
-    if not distributed and not args.watdiv and n_emu > 0:
+    if args.full and not distributed and not args.watdiv and n_emu > 0:
         import types
         log("[rank 0] embedded emulator leg...")
         emu_engines = [wk.Engine(gstore, device=local_rank) for _ in range(6)]
@@ -797,17 +913,17 @@ def main():
             del emu_engines
 
     cb = None
-    if (os.environ.get("WK_SKIP_CPU_BASELINE") != "1" and not distributed
-            and not args.watdiv):
+    if (args.full and os.environ.get("WK_SKIP_CPU_BASELINE") != "1"
+            and not distributed and not args.watdiv):
         log("[rank 0] timing cpu_baseline (oracle engine, same inputs)...")
         cb = cpu_baseline(nuniv, seed, triples=triples)
-        del triples
+    del triples
 
     latency = {}
     for name in names:
         xs = lat.get(name, [])
-        latency[name] = {"p50_ms": round(pctl(xs, 50), 3),
-                         "p99_ms": round(pctl(xs, 99), 3),
+        latency[name] = {"p50_ms": round(pctl(xs, 50), 3) if xs else None,
+                         "p99_ms": round(pctl(xs, 99), 3) if xs else None,
                          "rows": lat.get("_rows", {}).get(name)}
 
     out = {
@@ -819,6 +935,7 @@ def main():
         "n_gpus": ngpus,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(elapsed * 1e3 / args.steps, 3),
         "higher_is_better": True,
         "scaling": "strong",
@@ -851,6 +968,7 @@ def main():
                          for k in stats1},
     }
     print(json.dumps(out), flush=True)
+    log("[rank 0] result line printed")
     if distributed:
         dist.destroy_process_group()
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # One-command reproduction of every bench leg on a GPU box:
-#   1. headline LUBM-2560 Q1-Q7 suite (bench.py default; includes the
+#   1. headline LUBM-2560 Q1-Q7 suite (bench.py --full; includes the
 #      parity gates, roofline probe, same-input cpu_baseline and a short
 #      embedded emulator record in the same JSON line)
 #   2. full emulator light-mix leg (1M queries, batched windows)
@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 cd "$(dirname "$0")/.."
 
 echo "[bench_all] 1/3 LUBM-2560 suite" >&2
-python bench.py > "$OUT/bench_suite.json" 2> "$OUT/bench_suite.log"
+python bench.py --full > "$OUT/bench_suite.json" 2> "$OUT/bench_suite.log"
 
 echo "[bench_all] 2/3 emulator light-mix" >&2
 WK_SKIP_CPU_BASELINE=1 python bench.py --emu 1000000 \

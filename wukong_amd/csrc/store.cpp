@@ -35,7 +35,15 @@ using namespace wk;
 
 namespace {
 
-struct triple { sid_t s, p, o; };
+// The empty default constructor is deliberate: std::vector<triple>(n)
+// then leaves its storage untouched, so the multi-GB scratch arrays are
+// first written (and their pages first touched) by the parallel loops
+// that fill them instead of by a serial zero-fill.
+struct triple {
+    sid_t s, p, o;
+    triple() {}
+    triple(sid_t s_, sid_t p_, sid_t o_) : s(s_), p(p_), o(o_) {}
+};
 
 // parallel counting sort into buckets keyed by (p, id>>17), then per-bucket
 // std::sort — preserves full (p, major, minor) order because id>>17 is the
@@ -115,6 +123,13 @@ static void dedup_triples(std::vector<triple> &t) {
     auto eq = [](const triple &a, const triple &b) {
         return a.s == b.s && a.p == b.p && a.o == b.o;
     };
+    // parallel look first: the serial compaction is only needed when
+    // the sorted input really holds a duplicate
+    const int64_t n = (int64_t)t.size();
+    int64_t dups = 0;
+#pragma omp parallel for schedule(static) reduction(+ : dups)
+    for (int64_t i = 1; i < n; i++) dups += eq(t[i - 1], t[i]);
+    if (!dups) return;
     auto end = std::unique(t.begin(), t.end(), eq);
     t.erase(end, t.end());
 }
@@ -160,15 +175,32 @@ static wk_store_t *store_build_impl(const sid_t *spo, int64_t ntriples,
 
     // 1. partition into pso (s%n==sid) / pos (o%n==sid) — base_loader.hpp:344-352
     std::vector<triple> pso, pos;
-    pso.reserve(ntriples); pos.reserve(ntriples);
     uint32_t max_pid = 1, max_id = 0;
-    for (int64_t i = 0; i < ntriples; i++) {
-        triple t{spo[3 * i], spo[3 * i + 1], spo[3 * i + 2]};
-        max_pid = std::max(max_pid, t.p);
-        if (t.p == TYPE_ID) max_pid = std::max(max_pid, t.o);  // types are index ids
-        max_id = std::max({max_id, t.s, t.o});
-        if ((int32_t)(t.s % (sid_t)nsrv) == sid) pso.push_back(t);
-        if ((int32_t)(t.o % (sid_t)nsrv) == sid) pos.push_back(t);
+    if (nsrv == 1) {
+        // single partition: both orders take every triple, so the id
+        // maxima are a parallel reduction and the copies a parallel fill
+#pragma omp parallel for schedule(static) reduction(max : max_pid, max_id)
+        for (int64_t i = 0; i < ntriples; i++) {
+            const sid_t s = spo[3 * i], p = spo[3 * i + 1], o = spo[3 * i + 2];
+            max_pid = std::max(max_pid, p);
+            if (p == TYPE_ID) max_pid = std::max(max_pid, o);  // types are index ids
+            max_id = std::max({max_id, s, o});
+        }
+        pso.resize(ntriples);
+        pos.resize(ntriples);
+#pragma omp parallel for schedule(static)
+        for (int64_t i = 0; i < ntriples; i++)
+            pso[i] = pos[i] = triple(spo[3 * i], spo[3 * i + 1], spo[3 * i + 2]);
+    } else {
+        pso.reserve(ntriples); pos.reserve(ntriples);
+        for (int64_t i = 0; i < ntriples; i++) {
+            triple t{spo[3 * i], spo[3 * i + 1], spo[3 * i + 2]};
+            max_pid = std::max(max_pid, t.p);
+            if (t.p == TYPE_ID) max_pid = std::max(max_pid, t.o);  // types are index ids
+            max_id = std::max({max_id, t.s, t.o});
+            if ((int32_t)(t.s % (sid_t)nsrv) == sid) pso.push_back(t);
+            if ((int32_t)(t.o % (sid_t)nsrv) == sid) pos.push_back(t);
+        }
     }
     if (max_pid >= (1u << NBITS_IDX)) { delete st; return nullptr; }
     st->max_pid = max_pid;
@@ -199,22 +231,15 @@ static wk_store_t *store_build_impl(const sid_t *spo, int64_t ntriples,
     const uint32_t NP = max_pid + 1;
     std::vector<int64_t> pso_lo(NP + 1, 0), pos_lo(NP + 1, 0);
     {
-        int64_t i = 0;
+        // both arrays are sorted by p ascending (and every p <= max_pid),
+        // so slice p starts at the first element with predicate >= p
+        auto by_p = [](const triple &t, uint32_t p) { return t.p < p; };
         for (uint32_t p = 0; p <= max_pid; p++) {
-            pso_lo[p] = i;
-            while (i < (int64_t)pso.size() && pso[i].p == p) i++;
+            pso_lo[p] = std::lower_bound(pso.begin(), pso.end(), p, by_p) - pso.begin();
+            pos_lo[p] = std::lower_bound(pos.begin(), pos.end(), p, by_p) - pos.begin();
         }
         pso_lo[NP] = (int64_t)pso.size();
-        // pso is bucket-sorted by p ascending, so slices are contiguous —
-        // but only if every element was consumed:
-        if (i != (int64_t)pso.size()) { fprintf(stderr, "pso slice error\n"); abort(); }
-        i = 0;
-        for (uint32_t p = 0; p <= max_pid; p++) {
-            pos_lo[p] = i;
-            while (i < (int64_t)pos.size() && pos[i].p == p) i++;
-        }
         pos_lo[NP] = (int64_t)pos.size();
-        if (i != (int64_t)pos.size()) { fprintf(stderr, "pos slice error\n"); abort(); }
     }
 
     WK_LOG("[store] slices: %.1fs\n", now_s() - t0); t0 = now_s();
@@ -222,21 +247,26 @@ static wk_store_t *store_build_impl(const sid_t *spo, int64_t ntriples,
     //    OUT seg of pid: (s,p) runs in pso slice.
     //    IN  seg of pid: (o,p) runs in pos slice, skipping is_tpid(o) runs
     //    (type triples are never normal IN keys — static_gstore.hpp:128-131).
+    //    Parallel over the triples of each slice (a run head is an
+    //    element that differs from its predecessor), counted in
+    //    thread-private reductions: a few predicates hold most triples,
+    //    so per-predicate parallelism leaves most cores idle.
     std::vector<uint64_t> out_keys(NP, 0), out_edges(NP, 0), in_keys(NP, 0), in_edges(NP, 0);
-#pragma omp parallel for schedule(dynamic)
     for (uint32_t p = 0; p <= max_pid; p++) {
-        for (int64_t i = pso_lo[p]; i < pso_lo[p + 1];) {
-            int64_t j = i + 1;
-            while (j < pso_lo[p + 1] && pso[j].s == pso[i].s) j++;
-            out_keys[p]++; out_edges[p] += (uint64_t)(j - i);
-            i = j;
+        const int64_t slo = pso_lo[p], shi = pso_lo[p + 1];
+        const int64_t olo = pos_lo[p], ohi = pos_lo[p + 1];
+        uint64_t ok = 0, ik = 0, ie = 0;
+#pragma omp parallel for schedule(static) reduction(+ : ok) if (shi - slo > (1 << 16))
+        for (int64_t i = slo; i < shi; i++)
+            ok += (i == slo || pso[i].s != pso[i - 1].s);
+#pragma omp parallel for schedule(static) reduction(+ : ik, ie) if (ohi - olo > (1 << 16))
+        for (int64_t i = olo; i < ohi; i++) {
+            if (is_tpid(pos[i].o)) continue;
+            ie++;
+            ik += (i == olo || pos[i].o != pos[i - 1].o);
         }
-        for (int64_t i = pos_lo[p]; i < pos_lo[p + 1];) {
-            int64_t j = i + 1;
-            while (j < pos_lo[p + 1] && pos[j].o == pos[i].o) j++;
-            if (!is_tpid(pos[i].o)) { in_keys[p]++; in_edges[p] += (uint64_t)(j - i); }
-            i = j;
-        }
+        out_keys[p] = ok; out_edges[p] = (uint64_t)(shi - slo);
+        in_keys[p] = ik; in_edges[p] = ie;
     }
 
     st->seg_keys.assign((size_t)NP * 2, 0);
@@ -322,6 +352,18 @@ static wk_store_t *store_build_impl(const sid_t *spo, int64_t ntriples,
             int64_t j = i + 1;
             while (j < hi && (out ? arr[j].s : arr[j].o) == v) j++;
             if (!out && is_tpid(v)) { i = j; continue; }
+            // the slot array is far larger than any cache and every key
+            // lands in a random bucket: fetch the bucket of a key a few
+            // runs ahead while this one inserts (a hint only; a repeated
+            // or skipped key costs nothing but the hash)
+            if (j + 16 < hi) {
+                const sid_t nv = out ? arr[j + 16].s : arr[j + 16].o;
+                const char *nb = (const char *)&st->vertices[
+                    (sg.bucket_start +
+                     hash_u64(key_pack(nv, p, (uint64_t)dir)) % sg.num_buckets) * ASSOC];
+                __builtin_prefetch(nb, 1);
+                __builtin_prefetch(nb + 64, 1);
+            }
             uint64_t slot = ins.insert(key_pack(v, p, (uint64_t)dir));
             st->vertices[slot].ptr = ptr_pack((uint64_t)(j - i), off);
             for (int64_t k = i; k < j; k++)
@@ -335,6 +377,11 @@ static wk_store_t *store_build_impl(const sid_t *spo, int64_t ntriples,
     //    ours iterates pids ascending — deterministic where the reference's
     //    TBB iteration order was not; parity is set-level)
     {
+        // the keys insert serially in pid order (list offsets follow
+        // from the counts); the lists themselves fill in parallel
+        enum { SUBJECTS, MEMBERS, OBJECTS };
+        struct fill_t { int kind; uint32_t p; uint64_t off; };
+        std::vector<fill_t> fills;
         // IN: predicate-index (subjects) + type index
         if (st->iseg[DIR_IN].num_buckets) {
             inserter ins{*st, st->iseg[DIR_IN], ext_next};
@@ -343,19 +390,14 @@ static wk_store_t *store_build_impl(const sid_t *spo, int64_t ntriples,
                 if (out_keys[p]) {
                     uint64_t slot = ins.insert(key_pack(0, p, DIR_IN));
                     st->vertices[slot].ptr = ptr_pack(out_keys[p], off);
-                    for (int64_t i = pso_lo[p]; i < pso_lo[p + 1];) {
-                        int64_t j = i + 1;
-                        while (j < pso_lo[p + 1] && pso[j].s == pso[i].s) j++;
-                        st->edges[off++] = pso[i].s;
-                        i = j;
-                    }
+                    fills.push_back({SUBJECTS, p, off});
+                    off += out_keys[p];
                 }
                 if (type_members[p]) {
                     uint64_t slot = ins.insert(key_pack(0, p, DIR_IN));
                     st->vertices[slot].ptr = ptr_pack(type_members[p], off);
-                    // members in subject order (type slice is (s,o)-sorted)
-                    for (int64_t i = pso_lo[TYPE_ID]; i < pso_lo[TYPE_ID + 1]; i++)
-                        if (pso[i].o == p) st->edges[off++] = pso[i].s;
+                    fills.push_back({MEMBERS, p, off});
+                    off += type_members[p];
                 }
             }
         }
@@ -367,12 +409,27 @@ static wk_store_t *store_build_impl(const sid_t *spo, int64_t ntriples,
                 if (!in_keys[p]) continue;
                 uint64_t slot = ins.insert(key_pack(0, p, DIR_OUT));
                 st->vertices[slot].ptr = ptr_pack(in_keys[p], off);
-                for (int64_t i = pos_lo[p]; i < pos_lo[p + 1];) {
-                    int64_t j = i + 1;
-                    while (j < pos_lo[p + 1] && pos[j].o == pos[i].o) j++;
-                    if (!is_tpid(pos[i].o)) st->edges[off++] = pos[i].o;
-                    i = j;
-                }
+                fills.push_back({OBJECTS, p, off});
+                off += in_keys[p];
+            }
+        }
+#pragma omp parallel for schedule(dynamic)
+        for (size_t f = 0; f < fills.size(); f++) {
+            const uint32_t p = fills[f].p;
+            uint64_t off = fills[f].off;
+            if (fills[f].kind == SUBJECTS) {
+                for (int64_t i = pso_lo[p]; i < pso_lo[p + 1]; i++)
+                    if (i == pso_lo[p] || pso[i].s != pso[i - 1].s)
+                        st->edges[off++] = pso[i].s;
+            } else if (fills[f].kind == MEMBERS) {
+                // members in subject order (type slice is (s,o)-sorted)
+                for (int64_t i = pso_lo[TYPE_ID]; i < pso_lo[TYPE_ID + 1]; i++)
+                    if (pso[i].o == p) st->edges[off++] = pso[i].s;
+            } else {
+                for (int64_t i = pos_lo[p]; i < pos_lo[p + 1]; i++)
+                    if ((i == pos_lo[p] || pos[i].o != pos[i - 1].o) &&
+                        !is_tpid(pos[i].o))
+                        st->edges[off++] = pos[i].o;
             }
         }
     }
