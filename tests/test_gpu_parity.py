@@ -55,6 +55,57 @@ def test_side_index_fallback_parity(lubm4, oracle4):
                 os.environ[k] = v
 
 
+def test_wide_chain_all_column_counts():
+    """Every column-count instantiation the dispatcher can pick: an
+    8-variable chain and each of its prefixes (2..8 patterns, so the
+    expansions run with 1..7 input columns) against the oracle on
+    LUBM-1.  The fixed queries and the plan fuzzer stop at 5 variables.
+    Three ways: run_query on the default store (fn-map, CSR and scatter
+    kernels), graph replay on it (k_expand_fn_map and the other
+    hint-specialised expansions, by row count), and run_query on a store
+    without side indexes (k_probe_scan + k_expand_in/k_expand_big)."""
+    chain = [(Q.GRADSTUDENT, Q.TYPE_ID, wk.DIR_IN, -1),
+             (-1, Q.ADVISOR, wk.DIR_OUT, -2),
+             (-1, Q.MEMBEROF, wk.DIR_OUT, -3),
+             (-1, Q.UGDEGREE, wk.DIR_OUT, -4),
+             (-1, Q.TAKESCOURSE, wk.DIR_OUT, -5),
+             (-2, Q.TEACHEROF, wk.DIR_OUT, -6),
+             (-2, Q.NAME, wk.DIR_OUT, -7),
+             (-3, Q.SUBORG, wk.DIR_OUT, -8)]
+    plans = [Plan(chain[:n], nvars=n, required_vars=list(range(-1, -n - 1, -1)))
+             for n in range(2, 9)]
+    triples = wk.lubm_gen(1, seed=42)
+    ora = OracleCtx(triples)
+    want = [sort_rows(ora.run_query(p)) for p in plans]
+    assert want[-1].shape[0] > 0 and want[-1].shape[1] == 8
+
+    def check_rows(eng, how):
+        for p, w in zip(plans, want):
+            got = sort_rows(eng.run_query(p))
+            assert got.shape == w.shape, (how, p.nvars, got.shape, w.shape)
+            assert np.array_equal(got, w), (how, p.nvars)
+
+    eng = wk.Engine(wk.Store(triples), device=0)
+    check_rows(eng, "default")
+    for p, w in zip(plans, want):
+        gid = eng.graph_build(p)
+        for _ in range(2):
+            assert eng.graph_run(gid) == w.shape[0], ("graph", p.nvars)
+
+    old = {}
+    for k in ("WK_FN", "WK_CSR", "WK_TBM"):
+        old[k] = os.environ.get(k)
+        os.environ[k] = "0"
+    try:
+        check_rows(wk.Engine(wk.Store(triples), device=0), "no side index")
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
 def test_golden_fixture_gpu(eng4, store4):
     if not os.path.exists(GOLD):
         pytest.skip("golden fixture not generated")

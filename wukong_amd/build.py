@@ -17,9 +17,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 def build(force=False, verbose=True):
     if not force and os.path.exists(OUT):
-        newest = max(os.path.getmtime(s) for s in SRC + [
-            os.path.join(HERE, "csrc", "wk_types.h"),
-            os.path.join(HERE, "csrc", "wk_store.h")])
+        # every file in csrc/ (sources and the headers they include)
+        csrc = os.path.join(HERE, "csrc")
+        newest = max(os.path.getmtime(os.path.join(csrc, f))
+                     for f in os.listdir(csrc))
         if os.path.getmtime(OUT) > newest:
             if verbose:
                 print(f"wukong_amd.build: {OUT} up to date")

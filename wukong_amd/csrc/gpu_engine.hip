@@ -14,14 +14,20 @@
  * flag and the query is re-run at the larger capacity (replaces the
  * reference's hard 32 MB rbuf assert, gpu_engine_cuda.hpp:185).
  *
- * Kernel inventory:
+ * Kernel inventory (device code lives in the wk_kernels_*.h headers,
+ * included below: one translation unit):
+ *  wk_kernels_common.h
+ *   probe_one/probe_chain, bsearch_u32, tbm_has, csr_entry,
+ *   typeof_nodrop_ok — lookup helpers; d_state words and categories
+ *  wk_kernels_expand.h
  *   k_probe_scan      — fused gen-keys + thread-per-row cluster-hash
  *                       probe + in-kernel prefix scan (2-deep bucket
  *                       prefetch); replaces gpu_hash.cu:94-324
- *   k_filter_tpr      — fused probe/typeof filter + block compaction
- *                       (replaces gpu_hash.cu:326-445,523-585)
- *   k_light2          — whole-query single-kernel path for 2-pattern
- *                       light templates (emulator A1/A2/A3/A5)
+ *   k_csr_gather      — 24-B rank-compressed CSR probes for
+ *                       non-functional segments (vs 128-B bucket walks)
+ *   k_csr_gather_tf, k_expand_tf[_big] — EXACT fused k2u + typeof
+ *                       compaction over the CSR index (count pass ->
+ *                       scan -> filtered write)
  *   k_scan_local/mid  — chunked exclusive scan with DEVICE-side length
  *                       (replaces the thrust scans, gpu_hash.cu:587-596);
  *                       k_scan_mid also commits the step (S_INROWS
@@ -29,26 +35,33 @@
  *   k_expand_in/big   — input-centric expansion + wave-per-big-row pass
  *                       (replaces gpu_hash.cu:762-834; no 20-col cap),
  *                       optional inline no-drop typeof verify in graphs
- *   k_expand_tf[_big] — EXACT fused k2u + typeof compaction over the
- *                       CSR index (count pass -> scan -> filtered write)
- *   k_csr_gather      — 24-B rank-compressed CSR probes for
- *                       non-functional segments (vs 128-B bucket walks)
- *   zero-copy i2u/c2u — the 1-col start table IS the stored edge list
- *                       (read-only view; k_copy_list retired)
+ *   k_fn_gather/k_fn_scatter — functional-predicate rank-compressed
+ *                       map k2u (deg==1 segments; page+value gathers);
+ *                       k_expand_fn_map = optimistic 1:1 inside graphs
+ *   k_commit, k_commit_map, k_verify_commit, k_set_state, k_zero_words,
+ *   k_publish_state, k_project — 1-thread state kernels, projection
+ *  wk_kernels_filter.h
+ *   k_filter_tpr      — fused probe/typeof filter + block compaction
+ *                       (replaces gpu_hash.cu:326-445,523-585);
+ *                       per-type bitmaps: rdf:type filters read
+ *                       1 bit/vid (LLC-resident)
+ *   k_vu              — VERSATILE predicate-variable ops over the dense
+ *                       vp CSR (sparql.hpp:556-744)
+ *   k_expand_opt / k_filter_opt — OPTIONAL-group ops (BLANK fill,
+ *                       matched flags; sparql.hpp:100-170,316-375)
+ *  wk_kernels_batch.h
  *   k_dst_count/scan2/scatter2 — fork-join radix split by vid % ndst
  *                       (replaces gpu_hash.cu:600-760)
+ *   k_light2          — whole-query single-kernel path for 2-pattern
+ *                       light templates (emulator A1/A2/A3/A5)
  *   k_light_batch     — batched light-query window (one wavefront
  *                       workgroup per query; proxy.hpp:477-525 window)
  *   k_plan_batch      — LDS plan interpreter: whole multi-pattern
  *                       const-start templates, binding table in LDS
- *   k_vu              — VERSATILE predicate-variable ops over the dense
- *                       vp CSR (sparql.hpp:556-744)
- *   k_fn_gather/k_fn_scatter — functional-predicate rank-compressed
- *                       map k2u (deg==1 segments; page+value gathers);
- *                       k_expand_fn_map = optimistic 1:1 inside graphs
- *   k_expand_opt / k_filter_opt — OPTIONAL-group ops (BLANK fill,
- *                       matched flags; sparql.hpp:100-170,316-375)
- *   per-type bitmaps  — rdf:type filters read 1 bit/vid (LLC-resident)
+ *   k_peer_step       — xGMI peer-probe small-table step
+ *  host side (this file)
+ *   zero-copy i2u/c2u — the 1-col start table IS the stored edge list
+ *                       (read-only view, no copy kernel)
  *   hipGraph replay   — wk_engine_graph_build/run/launch: a fixed plan
  *                       replays as ONE launch, with warm-pass-derived
  *                       no-drop specialization verified on every replay
@@ -64,6 +77,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
+#include <type_traits>
 
 static double now_us() {
     return std::chrono::duration<double, std::micro>(
@@ -95,1802 +109,10 @@ enum {
     WK_ERR_CAP = -5,
 };
 
-// ---------------------------------------------------------------------
-// device kernels
-// ---------------------------------------------------------------------
-
-// probe modes
-enum { PK_NORMAL = 0, PK_INDEX = 1 };   // key = [vid|pid|dir] vs [0|val|dir]
-enum { PM_SIZE = 0,    // k2u: write edge count per row
-       PM_CONST = 1,   // k2c: flag = (const in edge list)
-       PM_COL = 2,     // k2k: flag = (row's other col in edge list)
-       PM_LIST = 3,    // c2k/i2k: flag = (row col value in a FIXED list)
-       PM_EQ = 4 };    // k2c via reversed functional map: flag = (col == cval)
-
-// device query state (see engine): [0]=nrows [1]=scan total [2]=overflow
-// flag [3]=required rows; stats[0..6] = algorithmic bytes per category
-enum { S_NROWS = 0, S_TOTAL = 1, S_ERR = 2, S_REQ = 3, S_OVF = 4,
-       S_DONE = 5, S_INROWS = 6, S_WORDS = 7 };
-enum { CAT_PROBE = 0, CAT_SCAN, CAT_EXPAND, CAT_FILTER, CAT_COPY, CAT_SPLIT,
-       CAT_OTHER, CAT_COUNT };
-
-constexpr int SCAN_T = 256;  // scan tile = block size of the fused kernels
-
-// Commit fused into the LAST finishing block of a producing kernel
-// (mode 1 = the k_commit semantics, 2 = k_commit_map).  MEASURED
-// NET-NEGATIVE for wide grids and disabled there (mode 0): 2048 blocks
-// bumping one done-word serialize at ~88 atomics/us (microarch row
-// `dequeue`) = ~23 us per kernel, more than the 1-thread commit
-// kernels cost (graph-q1 207 -> 257 us with fusion on).  Kept for
-// single-/small-grid kernels (k_peer_step commits inline).
-__device__ __forceinline__ void commit_tail(uint64_t *d_state, uint64_t cap,
-                                            int mode) {
-    if (!mode) return;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    unsigned long long done =
-        atomicAdd((unsigned long long *)&d_state[S_DONE], 1ull);
-    if (done + 1 != (unsigned long long)gridDim.x) return;
-    d_state[S_DONE] = 0;
-    uint64_t t = atomicAdd((unsigned long long *)&d_state[S_TOTAL], 0ull);
-    uint64_t ovf = atomicAdd((unsigned long long *)&d_state[S_OVF], 0ull);
-    if (mode == 2) {  // optimistic 1:1 map: rows unchanged, miss -> S_ERR
-        if (ovf) {
-            d_state[S_ERR] = 1;
-            d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
-        }
-    } else {
-        if (t > cap) {
-            d_state[S_ERR] = 1;
-            d_state[S_REQ] = max(d_state[S_REQ], t);
-            t = cap;
-        }
-        d_state[S_NROWS] = t;
-    }
-    d_state[S_TOTAL] = 0;
-    d_state[S_OVF] = 0;
-}
-
-__device__ __forceinline__ void count_bytes(uint64_t *stats, int cat,
-                                            uint64_t bytes) {
-    if (blockIdx.x == 0 && threadIdx.x == 0 && stats)
-        atomicAdd((unsigned long long *)&stats[cat], (unsigned long long)bytes);
-}
-
-// sorted-membership test: edge lists are ascending (loader sort,
-// base_loader.hpp:367-377) so binary search replaces the reference's
-// linear scan (sparql.hpp:430-470) with identical keep-row semantics.
-__device__ __forceinline__ bool bsearch_u32(const sid_t *a, uint64_t n, sid_t x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        uint64_t mid = (lo + hi) >> 1;
-        sid_t v = a[mid];
-        if (v < x) lo = mid + 1;
-        else if (v > x) hi = mid;
-        else return true;
-    }
-    return false;
-}
-
-// one cluster-hash lookup: walk the bucket chain, 7 slot compares per
-// 128-B bucket (gstore.hpp:341-361 semantics)
-__device__ __forceinline__ void probe_one(const vertex_t *__restrict__ verts,
-                                          uint64_t bucket_start,
-                                          uint64_t num_buckets, uint64_t key,
-                                          uint64_t &eoff, uint64_t &esz) {
-    uint64_t bucket = bucket_start + hash_u64(key) % num_buckets;
-    while (true) {
-        const vertex_t *b = &verts[bucket * ASSOC];
-        uint64_t k0 = b[0].key, k1 = b[1].key, k2 = b[2].key, k3 = b[3].key;
-        uint64_t k4 = b[4].key, k5 = b[5].key, k6 = b[6].key, k7 = b[7].key;
-        int hit = -1;
-        if (k0 == key) hit = 0;
-        else if (k1 == key) hit = 1;
-        else if (k2 == key) hit = 2;
-        else if (k3 == key) hit = 3;
-        else if (k4 == key) hit = 4;
-        else if (k5 == key) hit = 5;
-        else if (k6 == key) hit = 6;
-        if (hit >= 0) {
-            uint64_t pp = b[hit].ptr;
-            eoff = ptr_off(pp);
-            esz = ptr_size(pp);
-            return;
-        }
-        if (k7 == KEY_EMPTY) { eoff = 0; esz = 0; return; }
-        bucket = key_vid(k7);
-    }
-}
-
-// continue a probe from a chained bucket (absolute bucket id)
-__device__ __forceinline__ void probe_chain(const vertex_t *__restrict__ verts,
-                                            uint64_t bucket, uint64_t key,
-                                            uint64_t &eoff, uint64_t &esz) {
-    while (true) {
-        const vertex_t *b = &verts[bucket * ASSOC];
-        int hit = -1;
-#pragma unroll
-        for (int i = 0; i < ASSOC - 1; i++)
-            if (b[i].key == key && hit < 0) hit = i;
-        if (hit >= 0) {
-            eoff = ptr_off(b[hit].ptr);
-            esz = ptr_size(b[hit].ptr);
-            return;
-        }
-        if (b[ASSOC - 1].key == KEY_EMPTY) { eoff = 0; esz = 0; return; }
-        bucket = key_vid(b[ASSOC - 1].key);
-    }
-}
-
-// Fused known_to_unknown front half: contiguous-chunk thread-per-row
-// probe + in-kernel exclusive prefix of the edge counts (local prefix +
-// per-block sums; k_scan_mid finishes across blocks).  64 rows in
-// flight per wave between scan barriers — MLP for DRAM-random probes
-// (gstore.hpp:341-361; replaces gpu_hash.cu:94-324 + the thrust scan).
-__global__ void k_probe_scan(const vertex_t *__restrict__ verts,
-                             const sid_t *__restrict__ tbl, int ncols,
-                             int col, uint32_t pid, int dir, int key_mode,
-                             uint64_t bucket_start, uint64_t num_buckets,
-                             uint64_t *__restrict__ d_state,
-                             uint64_t *__restrict__ d_stats,
-                             uint64_t *__restrict__ d_eoff,
-                             uint32_t *__restrict__ d_cnt,
-                             uint64_t *__restrict__ d_pre,
-                             uint64_t *__restrict__ bsums)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 + 128 + 8 + 12));
-    const int64_t chunk = (nrows + gridDim.x - 1) / gridDim.x;
-    const int64_t start = (int64_t)blockIdx.x * chunk;
-    const int64_t end = min(start + chunk, nrows);
-    __shared__ uint64_t sh[SCAN_T];
-    uint64_t carry = 0;
-
-    // 2-deep pipeline: the NEXT tile row's first bucket is issued before
-    // this tile's scan phase, so its ~900-cycle HBM latency hides under
-    // the LDS scan + barriers (loads to registers stay in flight across
-    // s_barrier; hipcc waits at first use)
-    auto key_of = [&](int64_t r) {
-        sid_t v = tbl[r * ncols + col];
-        return (key_mode == PK_NORMAL) ? key_pack(v, pid, (uint64_t)dir)
-                                       : key_pack(0, v, (uint64_t)dir);
-    };
-    uint64_t nkey = 0, nbucket = 0;
-    uint64_t pk[ASSOC];
-    uint64_t pp[ASSOC - 1];
-    bool have_pref = false;
-    if (start + threadIdx.x < end) {
-        nkey = key_of(start + threadIdx.x);
-        nbucket = bucket_start + hash_u64(nkey) % num_buckets;
-        const vertex_t *b = &verts[nbucket * ASSOC];
-#pragma unroll
-        for (int i = 0; i < ASSOC; i++) pk[i] = b[i].key;
-#pragma unroll
-        for (int i = 0; i < ASSOC - 1; i++) pp[i] = b[i].ptr;
-        have_pref = true;
-    }
-    for (int64_t base = start; base < end; base += SCAN_T) {
-        const int64_t r = base + threadIdx.x;
-        uint64_t eoff = 0, esz = 0;
-        uint64_t key = nkey;
-        uint64_t ck[ASSOC], cp[ASSOC - 1];
-        bool have = have_pref;
-        if (have) {
-#pragma unroll
-            for (int i = 0; i < ASSOC; i++) ck[i] = pk[i];
-#pragma unroll
-            for (int i = 0; i < ASSOC - 1; i++) cp[i] = pp[i];
-        }
-        // issue next tile's first bucket
-        const int64_t rn = base + SCAN_T + threadIdx.x;
-        have_pref = false;
-        if (rn < end) {
-            nkey = key_of(rn);
-            nbucket = bucket_start + hash_u64(nkey) % num_buckets;
-            const vertex_t *b = &verts[nbucket * ASSOC];
-#pragma unroll
-            for (int i = 0; i < ASSOC; i++) pk[i] = b[i].key;
-#pragma unroll
-            for (int i = 0; i < ASSOC - 1; i++) pp[i] = b[i].ptr;
-            have_pref = true;
-        }
-        if (have) {
-            // resolve the prefetched bucket; rare chains fall back to the walk
-            int hit = -1;
-#pragma unroll
-            for (int i = 0; i < ASSOC - 1; i++)
-                if (ck[i] == key && hit < 0) hit = i;
-            if (hit >= 0) {
-                eoff = ptr_off(cp[hit]);
-                esz = ptr_size(cp[hit]);
-            } else if (ck[ASSOC - 1] != KEY_EMPTY) {
-                // rare (~13% of buckets): continue down the chain
-                probe_chain(verts, key_vid(ck[ASSOC - 1]), key, eoff, esz);
-            }
-            d_eoff[r] = eoff;
-            d_cnt[r] = (uint32_t)esz;
-        }
-        sh[threadIdx.x] = esz;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        if (r < end) d_pre[r] = carry + sh[threadIdx.x] - esz;
-        carry += sh[SCAN_T - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsums[blockIdx.x] = (start < end) ? carry : 0;
-}
-
-// CSR-indexed known_to_unknown front half (non-functional segments):
-// the 128-B cluster-hash bucket walk becomes a 16-B page + 8-B entry
-// lookup ({edge_off:40|len:24}, rank-compressed like the fn maps).
-// Two phases, following the two-phase fn lesson: a barrier-free 1:1
-// gather writes (eoff, cnt); k_scan_local then runs the chunked
-// prefix exactly as k_probe_scan produced it, so the expansion
-// kernels consume the identical layout.
-__global__ void k_csr_gather(const sid_t *__restrict__ tbl, int ncols,
-                             int col,
-                             const fnpage_t *__restrict__ pg,
-                             const uint64_t *__restrict__ entries,
-                             uint64_t base, uint64_t n,
-                             const uint64_t *__restrict__ d_state,
-                             uint64_t *__restrict__ d_stats,
-                             uint64_t *__restrict__ d_eoff,
-                             uint32_t *__restrict__ d_cnt)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 + 16 + 8 + 12));
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
-        sid_t v = tbl[r * ncols + col];
-        uint64_t e = 0;
-        uint64_t idx = (uint64_t)v - base;
-        if (idx < n) {
-            const fnpage_t p = pg[idx >> 6];
-            if ((p.bits >> (idx & 63)) & 1) {
-                uint32_t rk = p.rank +
-                              (uint32_t)__popcll(p.bits &
-                                                 ((1ull << (idx & 63)) - 1));
-                e = entries[rk];
-            }
-        }
-        d_eoff[r] = e >> 24;
-        d_cnt[r] = (uint32_t)(e & 0xFFFFFF);
-    }
-}
-
-// Counting variant for the EXACT fused `k2u + ?v rdf:type CONST`
-// compaction (nothing optimistic: output == expansion+filter output):
-// per row, CSR entry lookup, then ONE walk of the edge list counting
-// values whose type-bitmap bit is set.  d_cnt gets the FILTERED count
-// (the scan then yields exact output positions); d_eoff packs
-// {edge_off:40 | full_len:24} so the writer can re-walk the list.
-__global__ void k_csr_gather_tf(const sid_t *__restrict__ tbl, int ncols,
-                                int col,
-                                const fnpage_t *__restrict__ pg,
-                                const uint64_t *__restrict__ entries,
-                                uint64_t base, uint64_t n,
-                                const sid_t *__restrict__ edges,
-                                const uint64_t *__restrict__ tbm,
-                                uint64_t t_base, uint64_t t_n,
-                                const uint64_t *__restrict__ d_state,
-                                uint64_t *__restrict__ d_stats,
-                                uint64_t *__restrict__ d_eoff,
-                                uint32_t *__restrict__ d_cnt)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 + 16 + 8 + 12));
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
-        sid_t v = tbl[r * ncols + col];
-        uint64_t e = 0;
-        uint64_t idx = (uint64_t)v - base;
-        if (idx < n) {
-            const fnpage_t p = pg[idx >> 6];
-            if ((p.bits >> (idx & 63)) & 1) {
-                uint32_t rk = p.rank +
-                              (uint32_t)__popcll(p.bits &
-                                                 ((1ull << (idx & 63)) - 1));
-                e = entries[rk];
-            }
-        }
-        const uint64_t off = e >> 24;
-        const uint32_t len = (uint32_t)(e & 0xFFFFFF);
-        uint32_t keep = 0;
-        for (uint32_t k = 0; k < len; k++) {
-            uint64_t tix = (uint64_t)edges[off + k] - t_base;
-            keep += (tix < t_n && ((tbm[tix >> 6] >> (tix & 63)) & 1)) ? 1u
-                                                                       : 0u;
-        }
-        d_eoff[r] = e;  // {off:40|len:24} for the writer's re-walk
-        d_cnt[r] = keep;
-    }
-}
-
-// writer for the fused compaction: re-walk the edge list, emit only
-// passing values at the exact scanned positions (wave-ballot ranks for
-// the big-row pass below)
-template <int NC>
-__global__ void k_expand_tf(const sid_t *__restrict__ tbl, int ncols,
-                            const sid_t *__restrict__ edges,
-                            const uint64_t *__restrict__ d_eoff,
-                            const uint32_t *__restrict__ d_cnt,
-                            const uint64_t *__restrict__ d_pre,
-                            const uint64_t *__restrict__ bsums, int G,
-                            const uint64_t *__restrict__ tbm,
-                            uint64_t t_base, uint64_t t_n,
-                            uint64_t *__restrict__ d_state, uint64_t cap,
-                            uint64_t *__restrict__ d_stats,
-                            uint32_t *__restrict__ ovf,
-                            sid_t *__restrict__ out)
-{
-    const int64_t nrows = (int64_t)d_state[S_INROWS];
-    const int64_t chunk = (nrows + G - 1) / G;
-    constexpr int oc = NC + 1;
-    (void)ncols;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows;
-         r += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t keep = d_cnt[r];
-        if (!keep) continue;
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
-        if (basep >= cap) continue;
-        const uint64_t e = d_eoff[r];
-        const uint64_t off = e >> 24;
-        const uint32_t len = (uint32_t)(e & 0xFFFFFF);
-        if (len > 32) {
-            unsigned long long i = atomicAdd(
-                (unsigned long long *)&d_state[S_OVF], 1ull);
-            ovf[i] = (uint32_t)r;
-            continue;
-        }
-        sid_t row[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-        sid_t *dst = out + (int64_t)basep * oc;
-        uint32_t w = 0;
-        for (uint32_t k = 0; k < len && w < keep; k++) {
-            sid_t v = edges[off + k];
-            uint64_t tix = (uint64_t)v - t_base;
-            if (!(tix < t_n && ((tbm[tix >> 6] >> (tix & 63)) & 1))) continue;
-            if (basep + w >= cap) break;
-#pragma unroll
-            for (int c = 0; c < NC; c++) dst[c] = row[c];
-            dst[NC] = v;
-            dst += oc;
-            w++;
-        }
-    }
-}
-
-template <int NC>
-__global__ void k_expand_tf_big(const sid_t *__restrict__ tbl, int ncols,
-                                const sid_t *__restrict__ edges,
-                                const uint64_t *__restrict__ d_eoff,
-                                const uint32_t *__restrict__ d_cnt,
-                                const uint64_t *__restrict__ d_pre,
-                                const uint64_t *__restrict__ bsums, int G,
-                                const uint64_t *__restrict__ tbm,
-                                uint64_t t_base, uint64_t t_n,
-                                uint64_t *__restrict__ d_state, uint64_t cap,
-                                const uint32_t *__restrict__ ovf,
-                                sid_t *__restrict__ out)
-{
-    const int64_t nq = (int64_t)d_state[S_OVF];
-    const int64_t nrows = (int64_t)d_state[S_INROWS];
-    const int64_t chunk = (nrows + G - 1) / G;
-    constexpr int oc = NC + 1;
-    (void)ncols;
-    const int lane = threadIdx.x & 63;
-    const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t q = w0; q < nq; q += nw) {
-        const int64_t r = ovf[q];
-        const uint64_t e = d_eoff[r];
-        const uint64_t off = e >> 24;
-        const uint32_t len = (uint32_t)(e & 0xFFFFFF);
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
-        if (basep >= cap) continue;
-        sid_t row[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-        uint64_t wbase = 0;  // passing-rank base across 64-edge chunks
-        for (uint32_t k0 = 0; k0 < len; k0 += 64) {
-            const uint32_t k = k0 + lane;
-            bool pass = false;
-            sid_t v = 0;
-            if (k < len) {
-                v = edges[off + k];
-                uint64_t tix = (uint64_t)v - t_base;
-                pass = tix < t_n && ((tbm[tix >> 6] >> (tix & 63)) & 1);
-            }
-            uint64_t mask = __ballot(pass);
-            if (pass) {
-                uint64_t pos = basep + wbase +
-                               (uint64_t)__popcll(mask & ((1ull << lane) - 1));
-                if (pos < cap) {
-                    sid_t *dst = out + (int64_t)pos * oc;
-#pragma unroll
-                    for (int c = 0; c < NC; c++) dst[c] = row[c];
-                    dst[NC] = v;
-                }
-            }
-            wbase += (uint64_t)__popcll(mask);
-        }
-    }
-}
-
-// chunked exclusive prefix of d_cnt -> d_pre + per-chunk sums (same
-// chunk math as k_probe_scan so the expansion kernels are unchanged)
-__global__ void k_scan_local(const uint32_t *__restrict__ d_cnt,
-                             const uint64_t *__restrict__ d_state,
-                             uint64_t *__restrict__ d_pre,
-                             uint64_t *__restrict__ bsums)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    const int G = gridDim.x;
-    const int64_t chunk = (nrows + G - 1) / G;
-    const int64_t start = (int64_t)blockIdx.x * chunk;
-    const int64_t end = min(start + chunk, (int64_t)nrows);
-    __shared__ uint64_t sh[SCAN_T];
-    uint64_t carry = 0;
-    for (int64_t base = start; base < end; base += SCAN_T) {
-        const int64_t r = base + threadIdx.x;
-        uint64_t esz = (r < end) ? d_cnt[r] : 0;
-        sh[threadIdx.x] = esz;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        if (r < end) d_pre[r] = carry + sh[threadIdx.x] - esz;
-        carry += sh[SCAN_T - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsums[blockIdx.x] = (start < end) ? carry : 0;
-}
-
-// Filter predicate (k2c/k2k/c2k/i2k keep-row decision — the shared
-// core of the one-pass and scan-pipeline filter forms below).
-struct fparams {
-    const vertex_t *verts;
-    const sid_t *edges;
-    uint64_t bucket_start, num_buckets;
-    const sid_t *tbl;
-    int ncols, col;
-    uint32_t pid;
-    int dir, key_mode, probe_mode, col2;
-    sid_t cval;
-    uint64_t list_off, list_sz;
-    const uint16_t *type_of;
-    uint64_t type_base, type_n;
-    int use_typeof;
-    const uint64_t *tbm;
-    const fnpage_t *fn_pg;
-    const sid_t *fn_vals;
-    uint64_t fn_base, fn_n;
-    int fn_swap;
-};
-
-__device__ __forceinline__ bool filter_keep(const fparams &P, int64_t r) {
-    sid_t v = P.tbl[r * P.ncols + P.col];
-    if (P.use_typeof) {
-        uint64_t idx = (uint64_t)v - P.type_base;
-        if (P.tbm)
-            // per-type bitmap: 1 bit/vid, whole map LLC-resident —
-            // exact (multi-type included), no probe fallback
-            return idx < P.type_n && ((P.tbm[idx >> 6] >> (idx & 63)) & 1);
-        uint16_t t = (idx < P.type_n) ? P.type_of[idx] : 0;
-        if (t != 0xFFFF) return (sid_t)t == P.cval;
-    }
-    if (P.probe_mode == PM_EQ) {
-        // reversed functional map resolved host-side: the edge exists
-        // iff the row value IS the precomputed vertex
-        return v == P.cval;
-    }
-    if (P.probe_mode == PM_LIST && !P.use_typeof)
-        return bsearch_u32(P.edges + P.list_off, P.list_sz, v);
-    if (P.fn_pg) {
-        // functional predicate: the row's single object replaces the
-        // probe + edge-list search (rank-compressed map: 16-B page +
-        // 4-B value vs 148 bytes of hash traffic).  fn_swap: the
-        // REVERSED direction is functional — check fn[other col] == col.
-        sid_t a = v, b;
-        if (P.probe_mode == PM_CONST) b = P.cval;
-        else b = P.tbl[r * P.ncols + P.col2];
-        if (P.fn_swap) { sid_t t_ = a; a = b; b = t_; }
-        sid_t tv = fn_lookup(P.fn_pg, P.fn_vals, P.fn_base, P.fn_n, a);
-        return tv && tv == b;
-    }
-    uint64_t key = (P.key_mode == PK_NORMAL)
-                       ? key_pack(v, P.pid, (uint64_t)P.dir)
-                       : key_pack(0, v, (uint64_t)P.dir);
-    uint64_t eoff = 0, esz = 0;
-    probe_one(P.verts, P.bucket_start, P.num_buckets, key, eoff, esz);
-    sid_t tgt = (P.probe_mode == PM_CONST) ? P.cval
-                                           : P.tbl[r * P.ncols + P.col2];
-    return esz && bsearch_u32(P.edges + eoff, esz, tgt);
-}
-
-__device__ __forceinline__ uint64_t filter_bytes_per_row(const fparams &P) {
-    return (P.use_typeof ? 6
-            : P.fn_pg ? 24
-            : P.probe_mode == PM_LIST ? 12
-                                      : (4 + 128 + 8 + 64)) +
-           8 * P.ncols;
-}
-
-// One-pass filter: keep + wavefront-ballot compaction.  Each tile
-// costs ONE global cursor atomic per block — a single word saturates
-// at ~88 atomics/us (microarch row `dequeue`), so ~2048 in-flight
-// blocks serialize ~23 us per tile ROUND; fine up to ~1-2M rows.
-// (A flags+scan+scatter pipeline was tried for larger tables and
-// measured SLOWER at suite keep-rates — extra passes cost more than
-// the atomics they save.)  Row order is engine-internal; parity is
-// set-level (sparql.hpp:455-476 semantics).
-__global__ void k_filter_tpr(fparams P, int verify_only,
-                             int commit_mode, uint64_t commit_cap,
-                             uint64_t *__restrict__ d_state,
-                             uint64_t *__restrict__ d_stats,
-                             sid_t *__restrict__ out_tbl)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * filter_bytes_per_row(P));
-    constexpr int K = 4;
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned int s_cnt;
-    __shared__ unsigned int s_wbase[SCAN_T / 64];
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int ncols = P.ncols;
-    const sid_t *__restrict__ tbl = P.tbl;
-    const int64_t tile = (int64_t)blockDim.x * K;
-    const int64_t stride = (int64_t)gridDim.x * tile;
-
-    for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows; base += stride) {
-        bool keep[K];
-        int64_t rr[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const int64_t r = base + k * SCAN_T + threadIdx.x;
-            rr[k] = r;
-            keep[k] = r < nrows && filter_keep(P, r);
-        }
-        if (verify_only) {
-            // identity-verified filter (captured graphs): the warm pass
-            // saw zero drops; every replay still checks every row and
-            // flags S_ERR on any miss (no writes, no table flip)
-            uint32_t miss = 0;
-#pragma unroll
-            for (int k = 0; k < K; k++)
-                miss += (rr[k] < nrows && !keep[k]) ? 1u : 0u;
-            if (miss)
-                atomicAdd((unsigned long long *)&d_state[S_OVF],
-                          (unsigned long long)miss);
-            continue;
-        }
-        if (threadIdx.x == 0) s_cnt = 0;
-        __syncthreads();
-        uint64_t mask[K];
-        uint32_t wtot = 0;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            mask[k] = __ballot(keep[k]);
-            wtot += (uint32_t)__popcll(mask[k]);
-        }
-        if (lane == 0) s_wbase[wid] = atomicAdd(&s_cnt, wtot);
-        __syncthreads();
-        if (threadIdx.x == 0)
-            s_base = s_cnt ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
-                                       (unsigned long long)s_cnt)
-                           : 0;
-        __syncthreads();
-        uint32_t wpos = s_wbase[wid];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            if (keep[k]) {
-                uint64_t pos = s_base + wpos +
-                               (uint32_t)__popcll(mask[k] &
-                                                  ((1ull << lane) - 1));
-                sid_t *dst = out_tbl + (int64_t)pos * ncols;
-                const sid_t *srow = tbl + rr[k] * ncols;
-                for (int c = 0; c < ncols; c++) dst[c] = srow[c];
-            }
-            wpos += (uint32_t)__popcll(mask[k]);
-        }
-    }
-    commit_tail(d_state, commit_cap, commit_mode);
-}
-
-// fn-expansion scatter (phase 4 of gather -> scan_local -> scan_mid ->
-// scatter): deterministic positions, no atomics, barrier-free.
-template <int NC>
-__global__ void k_fn_scatter(const sid_t *__restrict__ tbl,
-                             const sid_t *__restrict__ d_val,
-                             const uint32_t *__restrict__ d_cnt,
-                             const uint64_t *__restrict__ d_pre,
-                             const uint64_t *__restrict__ bsums, int G,
-                             const uint64_t *__restrict__ d_state,
-                             uint64_t *__restrict__ d_stats,
-                             sid_t *__restrict__ out)
-{
-    const int64_t nrows = (int64_t)d_state[S_INROWS];  // scan_mid committed
-    constexpr int oc = NC + 1;
-    count_bytes(d_stats, CAT_EXPAND, (uint64_t)nrows * (4 + 4 * NC + 4 * oc));
-    const int64_t chunk = (nrows + G - 1) / G;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
-        if (!d_cnt[r]) continue;
-        uint64_t pos = d_pre[r] + bsums[r / chunk];
-        sid_t *dst = out + (int64_t)pos * oc;
-        const sid_t *srow = tbl + r * NC;
-#pragma unroll
-        for (int c = 0; c < NC; c++) dst[c] = srow[c];
-        dst[NC] = d_val[r];
-    }
-}
-
-// finish the scan across blocks: exclusive over the G block sums
-// (single block).  Fuses the step commit (k_commit semantics): the
-// pipeline total is known here, the following scatter kernels read
-// the INPUT row count from the S_INROWS snapshot, and S_OVF (the
-// big-row queue this chain is about to fill) starts clean — saving
-// the separate 1-thread commit launch per k2u/fn step.
-__global__ void k_scan_mid(uint64_t *__restrict__ bsums, int G,
-                           uint64_t cap, uint64_t *__restrict__ d_state)
-{
-    __shared__ uint64_t sh[SCAN_T];
-    uint64_t carry = 0;
-    for (int base = 0; base < G; base += SCAN_T) {
-        int i = base + threadIdx.x;
-        uint64_t x = (i < G) ? bsums[i] : 0;
-        sh[threadIdx.x] = x;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t v = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += v;
-            __syncthreads();
-        }
-        if (i < G) bsums[i] = carry + sh[threadIdx.x] - x;
-        carry += sh[SCAN_T - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        d_state[S_INROWS] = d_state[S_NROWS];
-        uint64_t t = carry;
-        if (t > cap) {
-            d_state[S_ERR] = 1;
-            d_state[S_REQ] = max(d_state[S_REQ], t);
-            t = cap;
-        }
-        d_state[S_NROWS] = t;
-        d_state[S_TOTAL] = 0;
-        d_state[S_OVF] = 0;
-    }
-}
-
-// advance: nrows = min(total, cap); flag overflow for the host re-run
-// (replaces the reference's rbuf-overflow assert, gpu_engine_cuda.hpp:185)
-__global__ void k_commit(uint64_t *__restrict__ d_state, uint64_t cap) {
-    uint64_t t = d_state[S_TOTAL];
-    if (t > cap) {
-        d_state[S_ERR] = 1;
-        d_state[S_REQ] = max(d_state[S_REQ], t);
-        t = cap;
-    }
-    d_state[S_NROWS] = t;
-    // reset the accumulators for the next step (saves a 3us k_zero_words
-    // launch per step — the state kernels were 12% of suite GPU time)
-    d_state[S_TOTAL] = 0;
-    d_state[S_OVF] = 0;
-}
-
-__global__ void k_set_state(uint64_t *__restrict__ d_state, uint64_t nrows) {
-    d_state[S_NROWS] = nrows;
-    d_state[S_TOTAL] = 0;
-    d_state[S_OVF] = 0;
-}
-
-// device projection to required-var columns (sparql.hpp:1510-1536)
-struct cols8 { int32_t c[8]; };
-__global__ void k_project(const sid_t *__restrict__ tbl, int ncols,
-                          const uint64_t *__restrict__ d_state, cols8 cols,
-                          int rc, sid_t *__restrict__ out)
-{
-    const int64_t n = (int64_t)d_state[S_NROWS];
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * rc;
-         t += (int64_t)gridDim.x * blockDim.x) {
-        int64_t i = t / rc;
-        int j = (int)(t - i * rc);
-        int c = cols.c[j];
-        out[t] = (c >= 0) ? tbl[i * ncols + c] : (sid_t)0xFFFFFFFFu;
-    }
-}
-
-__global__ void k_publish_state(const uint64_t *__restrict__ d_state,
-                                const uint64_t *__restrict__ d_stats,
-                                uint64_t *__restrict__ h_pin) {
-    for (int i = 0; i < S_WORDS; i++) h_pin[i] = d_state[i];
-    for (int i = 0; i < CAT_COUNT; i++) h_pin[8 + i] = d_stats[i];
-    // sticky error flag (h_pin slot 7): survives across back-to-back
-    // graph replays whose own begin kernels clear d_state — the
-    // one-sync-per-pass path checks and clears it host-side
-    if (d_state[S_ERR]) h_pin[7] = 1;
-}
-
-// Input-centric expansion (known_to_unknown back half,
-// sparql.hpp:325-367): thread r writes its deg outputs at
-// pre[r]+bsums[chunk(r)] — no per-output binary search (the
-// output-centric version paid 2-3 DRAM lines of prefix walk per output
-// row).  Rows with deg > 32 go to an overflow queue handled by
-// k_expand_big with one WAVE per row (lanes stride the edge list).
-// verify-fused expansion (captured graphs only): when the NEXT pattern
-// is a no-drop `?v rdf:type CONST` filter on the NEW column (warm-pass
-// hint), each written value is checked inline (bitmap or dense type_of;
-// misses count into S_DONE -> k_verify_commit -> S_ERR -> safe re-run)
-// and the separate full-table verify pass disappears.
-template <int NC>
-__global__ void k_expand_in(const sid_t *__restrict__ tbl, int ncols,
-                            const sid_t *__restrict__ edges,
-                            const uint64_t *__restrict__ d_eoff,
-                            const uint32_t *__restrict__ d_cnt,
-                            const uint64_t *__restrict__ d_pre,
-                            const uint64_t *__restrict__ bsums, int G,
-                            uint64_t *__restrict__ d_state, uint64_t cap,
-                            uint64_t *__restrict__ d_stats,
-                            uint32_t *__restrict__ ovf,
-                            const uint64_t *__restrict__ vtbm,
-                            const uint16_t *__restrict__ v_type_of,
-                            uint64_t v_type_base, uint64_t v_type_n,
-                            sid_t v_cval, int verify,
-                            sid_t *__restrict__ out)
-{
-    // k_scan_mid already committed: S_INROWS = the input row count,
-    // S_NROWS = the (capped) output total
-    const int64_t nrows = (int64_t)d_state[S_INROWS];
-    const int64_t chunk = (nrows + G - 1) / G;
-    constexpr int oc = NC + 1;
-    (void)ncols;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows;
-         r += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t deg = d_cnt[r];
-        if (!deg) continue;
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
-        if (basep >= cap) continue;  // overflow: flagged by k_commit
-        if (deg > 32) {
-            unsigned long long i = atomicAdd(
-                (unsigned long long *)&d_state[S_OVF], 1ull);
-            ovf[i] = (uint32_t)r;
-            continue;
-        }
-        if (basep + deg > cap) deg = (uint32_t)(cap - basep);
-        sid_t row[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-        const sid_t *el = edges + d_eoff[r];
-        sid_t *dst = out + (int64_t)basep * oc;
-        uint32_t miss = 0;
-        for (uint32_t k = 0; k < deg; k++) {
-#pragma unroll
-            for (int c = 0; c < NC; c++) dst[c] = row[c];
-            sid_t v = el[k];
-            dst[NC] = v;
-            dst += oc;
-            if (verify) {
-                uint64_t tix = (uint64_t)v - v_type_base;
-                bool ok;
-                if (vtbm) {
-                    ok = tix < v_type_n && ((vtbm[tix >> 6] >> (tix & 63)) & 1);
-                } else {
-                    uint16_t t = (tix < v_type_n) ? v_type_of[tix] : 0;
-                    ok = t != 0xFFFF && (sid_t)t == v_cval;
-                }
-                miss += ok ? 0u : 1u;
-            }
-        }
-        if (miss)
-            atomicAdd((unsigned long long *)&d_state[S_DONE],
-                      (unsigned long long)miss);
-    }
-    // algorithmic bytes for the whole expansion (counted once; includes
-    // the big-row pass): total*(edge 4 + write 4*oc) + nrows*(row 4*ncols
-    // + cnt/pre/eoff 20)
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        atomicAdd((unsigned long long *)&d_stats[CAT_EXPAND],
-                  (unsigned long long)(d_state[S_NROWS] * (4 + 4 * oc) +
-                                       (uint64_t)nrows * (4 * ncols + 20)));
-}
-
-// big-fanout rows: one wave per queued row, lanes stride the edge list
-// (coalesced writes: adjacent lanes write adjacent output rows)
-template <int NC>
-__global__ void k_expand_big(const sid_t *__restrict__ tbl, int ncols,
-                             const sid_t *__restrict__ edges,
-                             const uint64_t *__restrict__ d_eoff,
-                             const uint32_t *__restrict__ d_cnt,
-                             const uint64_t *__restrict__ d_pre,
-                             const uint64_t *__restrict__ bsums, int G,
-                             uint64_t *__restrict__ d_state, uint64_t cap,
-                             int commit_mode,
-                             const uint32_t *__restrict__ ovf,
-                             const uint64_t *__restrict__ vtbm,
-                             const uint16_t *__restrict__ v_type_of,
-                             uint64_t v_type_base, uint64_t v_type_n,
-                             sid_t v_cval, int verify,
-                             sid_t *__restrict__ out)
-{
-    const int64_t nq = (int64_t)d_state[S_OVF];
-    const int64_t nrows = (int64_t)d_state[S_INROWS];
-    const int64_t chunk = (nrows + G - 1) / G;
-    constexpr int oc = NC + 1;
-    (void)ncols;
-    const int lane = threadIdx.x & 63;
-    const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t q = w0; q < nq; q += nw) {
-        const int64_t r = ovf[q];
-        uint64_t deg = d_cnt[r];
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
-        if (basep >= cap) continue;
-        if (basep + deg > cap) deg = cap - basep;
-        sid_t row[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-        const sid_t *el = edges + d_eoff[r];
-        uint32_t miss = 0;
-        for (uint64_t k = lane; k < deg; k += 64) {
-            sid_t *dst = out + (int64_t)(basep + k) * oc;
-#pragma unroll
-            for (int c = 0; c < NC; c++) dst[c] = row[c];
-            sid_t v = el[k];
-            dst[NC] = v;
-            if (verify) {
-                uint64_t tix = (uint64_t)v - v_type_base;
-                bool ok;
-                if (vtbm) {
-                    ok = tix < v_type_n && ((vtbm[tix >> 6] >> (tix & 63)) & 1);
-                } else {
-                    uint16_t t = (tix < v_type_n) ? v_type_of[tix] : 0;
-                    ok = t != 0xFFFF && (sid_t)t == v_cval;
-                }
-                miss += ok ? 0u : 1u;
-            }
-        }
-        if (miss)
-            atomicAdd((unsigned long long *)&d_state[S_DONE],
-                      (unsigned long long)miss);
-    }
-    commit_tail(d_state, cap, commit_mode);
-}
-
-// known_to_unknown over a FUNCTIONAL predicate (every key deg==1,
-// rank-compressed map): the probe+scan+expand pipeline collapses into
-// a page+value gather pair + compacted append, with an optional fused
-// `?v rdf:type CONST` filter on the NEW column (plan pairs like Q1's
-// ugDegreeFrom -> University).  Two phases: a 1:1 grid-stride GATHER
-// (the measured-fast k_expand_fn_map shape — no barriers between the
-// dependent page/value loads) writes each row's resolved object (0 =
-// miss/filtered) to a scratch stream; the COMPACT phase then reads it
-// SEQUENTIALLY with the block-aggregated scan.  The round-1 single-pass
-// form interleaved the gathers with 16 scan barriers per tile and ran
-// 4-5x slower than its own gather cost (169 vs 36 us on Q1's 6.4M-row
-// step).  Multi-type (0xFFFF) falls back to a probe of [val|TYPE|OUT].
-// Output rows <= input rows, so capacity can never overflow.
-__global__ void k_fn_gather(const sid_t *__restrict__ tbl, int ncols,
-                            const fnpage_t *__restrict__ fn_pg,
-                            const sid_t *__restrict__ fn_vals,
-                            uint64_t fn_base, uint64_t fn_n, int col,
-                            int use_typeof, sid_t fcval,
-                            const uint16_t *__restrict__ type_of,
-                            const uint64_t *__restrict__ tbm,
-                            uint64_t type_base, uint64_t type_n,
-                            const vertex_t *__restrict__ verts,
-                            const sid_t *__restrict__ edges,
-                            uint64_t f_bstart, uint64_t f_nbuckets,
-                            const uint64_t *__restrict__ d_state,
-                            uint64_t *__restrict__ d_stats,
-                            sid_t *__restrict__ d_val,
-                            uint32_t *__restrict__ d_cnt)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    count_bytes(d_stats, CAT_EXPAND,
-                (uint64_t)nrows * (24 + 4 + (use_typeof ? 2 : 0)));
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
-        sid_t v = tbl[r * ncols + col];
-        sid_t tv = fn_lookup(fn_pg, fn_vals, fn_base, fn_n, v);
-        if (tv && use_typeof) {
-            uint64_t tix = (uint64_t)tv - type_base;
-            if (tbm) {  // bitmap: decision is exact (multi-type incl.)
-                if (!(tix < type_n && ((tbm[tix >> 6] >> (tix & 63)) & 1)))
-                    tv = 0;
-            } else {
-                uint16_t t = (tix < type_n) ? type_of[tix] : 0;
-                if (t != 0xFFFF) {
-                    if ((sid_t)t != fcval) tv = 0;
-                } else {
-                    uint64_t eo = 0, es = 0;
-                    probe_one(verts, f_bstart, f_nbuckets,
-                              key_pack(tv, TYPE_ID, (uint64_t)DIR_OUT), eo,
-                              es);
-                    if (!(es && bsearch_u32(edges + eo, es, fcval))) tv = 0;
-                }
-            }
-        }
-        d_val[r] = tv;
-        d_cnt[r] = tv ? 1u : 0u;
-    }
-}
-
-// Fused known_to_unknown + rdf:type constant filter on the NEW column
-// (plan pairs like Q1's ugDegreeFrom -> "?Y type University"): expansion
-// emits only passing rows, block-compacted — saves the follow-up
-// filter's full table read+write pass.  Multi-type entities (0xFFFF)
-// fall back to a probe of [val|TYPE_ID|OUT].
-template <int NC>
-__global__ void k_expand_filter(const sid_t *__restrict__ tbl, int ncols,
-                                const sid_t *__restrict__ edges,
-                                const uint64_t *__restrict__ d_eoff,
-                                const uint32_t *__restrict__ d_cnt,
-                                uint64_t *__restrict__ d_state, uint64_t cap,
-                                uint64_t *__restrict__ d_stats,
-                                uint32_t *__restrict__ ovf,
-                                sid_t fcval,
-                                const uint16_t *__restrict__ type_of,
-                                uint64_t type_base, uint64_t type_n,
-                                const vertex_t *__restrict__ verts,
-                                uint64_t f_bstart, uint64_t f_nbuckets,
-                                sid_t *__restrict__ out)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    constexpr int oc = NC + 1;
-    (void)ncols;
-    count_bytes(d_stats, CAT_EXPAND,
-                (uint64_t)nrows * (4 * NC + 20) + d_state[S_TOTAL] * 6);
-    __shared__ unsigned long long s_base;
-    __shared__ uint32_t sh[SCAN_T];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    auto pass = [&](sid_t val) {
-        uint64_t idx = (uint64_t)val - type_base;
-        uint16_t t = (idx < type_n) ? type_of[idx] : 0;
-        if (t != 0xFFFF) return (sid_t)t == fcval;
-        uint64_t eo = 0, es = 0;
-        probe_one(verts, f_bstart, f_nbuckets,
-                  key_pack(val, TYPE_ID, (uint64_t)DIR_OUT), eo, es);
-        return es && bsearch_u32(edges + eo, es, fcval);
-    };
-    // fast path handles deg <= DF with fixed-index registers (a runtime-
-    // indexed local array goes to scratch — HIP guide rule 20); bigger
-    // rows go to the wave pass.  All of a thread's edge+type loads issue
-    // before any compare, so their latencies overlap.
-    constexpr int DF = 4;
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < nrows;
-         base += stride) {
-        const int64_t r = base + threadIdx.x;
-        sid_t ev[DF];
-        bool pv[DF];
-        uint32_t deg = 0, cnt = 0;
-        if (r < nrows) {
-            deg = d_cnt[r];
-            if (deg > DF) {
-                unsigned long long i = atomicAdd(
-                    (unsigned long long *)&d_state[S_OVF], 1ull);
-                ovf[i] = (uint32_t)r;
-                deg = 0;
-            } else if (deg) {
-                const sid_t *el = edges + d_eoff[r];
-#pragma unroll
-                for (int k = 0; k < DF; k++)
-                    ev[k] = (k < (int)deg) ? el[k] : 0;
-#pragma unroll
-                for (int k = 0; k < DF; k++)
-                    pv[k] = (k < (int)deg) && pass(ev[k]);
-#pragma unroll
-                for (int k = 0; k < DF; k++) cnt += pv[k] ? 1u : 0u;
-            }
-        }
-        sh[threadIdx.x] = cnt;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint32_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        const uint32_t my_end = sh[threadIdx.x];
-        const uint32_t btot = sh[SCAN_T - 1];
-        if (threadIdx.x == SCAN_T - 1)
-            s_base = btot ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
-                                      (unsigned long long)btot)
-                          : 0;
-        __syncthreads();
-        if (cnt) {
-            uint64_t pos = s_base + my_end - cnt;
-            sid_t row[NC];
-#pragma unroll
-            for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-#pragma unroll
-            for (int k = 0; k < DF; k++) {
-                if (!pv[k] || pos >= cap) continue;
-                sid_t *dst = out + (int64_t)pos * oc;
-#pragma unroll
-                for (int c = 0; c < NC; c++) dst[c] = row[c];
-                dst[NC] = ev[k];
-                pos++;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// big-fanout rows of the fused path: one wave per row, ballot compaction,
-// one atomic per 64 edges
-template <int NC>
-__global__ void k_expand_filter_big(const sid_t *__restrict__ tbl, int ncols,
-                                    const sid_t *__restrict__ edges,
-                                    const uint64_t *__restrict__ d_eoff,
-                                    const uint32_t *__restrict__ d_cnt,
-                                    uint64_t *__restrict__ d_state, uint64_t cap,
-                                    const uint32_t *__restrict__ ovf,
-                                    sid_t fcval,
-                                    const uint16_t *__restrict__ type_of,
-                                    uint64_t type_base, uint64_t type_n,
-                                    const vertex_t *__restrict__ verts,
-                                    uint64_t f_bstart, uint64_t f_nbuckets,
-                                    sid_t *__restrict__ out)
-{
-    const int64_t nq = (int64_t)d_state[S_OVF];
-    if (!nq) return;
-    constexpr int oc = NC + 1;
-    (void)ncols;
-    const int lane = threadIdx.x & 63;
-    const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t q = w0; q < nq; q += nw) {
-        const int64_t r = ovf[q];
-        const uint64_t deg = d_cnt[r];
-        const sid_t *el = edges + d_eoff[r];
-        sid_t row[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-        for (uint64_t k0 = 0; k0 < deg; k0 += 64) {
-            uint64_t k = k0 + lane;
-            sid_t v = 0;
-            bool keep = false;
-            if (k < deg) {
-                v = el[k];
-                uint64_t idx = (uint64_t)v - type_base;
-                uint16_t t = (idx < type_n) ? type_of[idx] : 0;
-                if (t != 0xFFFF) {
-                    keep = ((sid_t)t == fcval);
-                } else {
-                    uint64_t eo = 0, es = 0;
-                    probe_one(verts, f_bstart, f_nbuckets,
-                              key_pack(v, TYPE_ID, (uint64_t)DIR_OUT), eo, es);
-                    keep = es && bsearch_u32(edges + eo, es, fcval);
-                }
-            }
-            uint64_t m = __ballot(keep);
-            int wcnt = __popcll(m);
-            unsigned long long wbase = 0;
-            if (lane == 0 && wcnt)
-                wbase = atomicAdd((unsigned long long *)&d_state[S_TOTAL],
-                                  (unsigned long long)wcnt);
-            wbase = __shfl((unsigned long long)wbase, 0);
-            if (keep) {
-                uint64_t pos = wbase + __popcll(m & ((1ull << lane) - 1));
-                if (pos < cap) {
-                    sid_t *dst = out + (int64_t)pos * oc;
-#pragma unroll
-                    for (int c = 0; c < NC; c++) dst[c] = row[c];
-                    dst[NC] = v;
-                }
-            }
-        }
-    }
-}
-
-// i2u / c2u: materialise an edge/index list as a 1-column table
-
-// fork-join split (generate_sub_query sparql.hpp:772-796): dst = vid % ndst
-// Fork-join split as a radix partition (replaces the per-row
-// global-cursor scatter: 6.4M rows over <=8 cursor words serialize at
-// ~88 atomics/us per word ~= 9 ms; reference analog
-// gpu_hash.cu:600-760).  Phase 1: per-block LDS histograms over
-// contiguous chunks; phase 2: ONE block turns them into per-
-// (block,dst) bases + per-dst totals; phase 3: scatter with LDS
-// cursors only — no global atomics anywhere.
-__global__ void k_dst_count(const sid_t *__restrict__ tbl, int64_t nrows,
-                            int ncols, int col, int ndst,
-                            unsigned long long *__restrict__ bh)
-{
-    __shared__ unsigned int lh[64];
-    const int G = gridDim.x;
-    const int64_t chunk = (nrows + G - 1) / G;
-    const int64_t start = (int64_t)blockIdx.x * chunk;
-    const int64_t end = min(start + chunk, nrows);
-    if (threadIdx.x < 64) lh[threadIdx.x] = 0;
-    __syncthreads();
-    for (int64_t r = start + threadIdx.x; r < end; r += blockDim.x)
-        atomicAdd(&lh[tbl[r * ncols + col] % (sid_t)ndst], 1u);
-    __syncthreads();
-    if (threadIdx.x < (unsigned)ndst)
-        bh[(size_t)blockIdx.x * ndst + threadIdx.x] = lh[threadIdx.x];
-}
-
-__global__ void k_dst_scan2(unsigned long long *__restrict__ bh, int G,
-                            int ndst, unsigned long long *__restrict__ hist)
-{
-    __shared__ unsigned long long tot[64];
-    const int d = threadIdx.x;
-    if (d < ndst) {
-        unsigned long long run = 0;
-        for (int b = 0; b < G; b++) {
-            unsigned long long t = bh[(size_t)b * ndst + d];
-            bh[(size_t)b * ndst + d] = run;
-            run += t;
-        }
-        tot[d] = run;
-        hist[d] = run;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long acc = 0;
-        for (int i = 0; i < ndst; i++) {
-            unsigned long long t = tot[i];
-            tot[i] = acc;
-            acc += t;
-        }
-    }
-    __syncthreads();
-    if (d < ndst)
-        for (int b = 0; b < G; b++) bh[(size_t)b * ndst + d] += tot[d];
-}
-
-__global__ void k_dst_scatter2(const sid_t *__restrict__ tbl, int64_t nrows,
-                               int ncols, int col, int ndst,
-                               const unsigned long long *__restrict__ bh,
-                               sid_t *__restrict__ out)
-{
-    __shared__ unsigned int lc[64];
-    const int G = gridDim.x;
-    const int64_t chunk = (nrows + G - 1) / G;
-    const int64_t start = (int64_t)blockIdx.x * chunk;
-    const int64_t end = min(start + chunk, nrows);
-    if (threadIdx.x < 64) lc[threadIdx.x] = 0;
-    __syncthreads();
-    for (int64_t r = start + threadIdx.x; r < end; r += blockDim.x) {
-        int d = (int)(tbl[r * ncols + col] % (sid_t)ndst);
-        unsigned long long pos = bh[(size_t)blockIdx.x * ndst + d] +
-                                 atomicAdd(&lc[d], 1u);
-        sid_t *dst = out + pos * ncols;
-        const sid_t *src = tbl + r * ncols;
-        for (int c = 0; c < ncols; c++) dst[c] = src[c];
-    }
-}
-
-// whole-query fast path for the dominant light-template shape
-// (const_to_unknown + rdf:type constant filter — emulator A1/A2/A3/A5,
-// proxy.hpp:391-545): ONE single-block kernel executes both patterns and
-// publishes the row count straight to pinned memory.  Cuts ~20 dispatches
-// to 1 (the launch rate, not the kernels, bounds light-query throughput).
-__global__ void k_light2(const sid_t *__restrict__ edges, uint64_t list_off,
-                         uint64_t sz, sid_t cval,
-                         const uint16_t *__restrict__ type_of,
-                         uint64_t type_base, uint64_t type_n,
-                         uint64_t *__restrict__ d_state,
-                         uint64_t *__restrict__ d_stats,
-                         sid_t *__restrict__ out,
-                         uint64_t *__restrict__ h_pin)
-{
-    __shared__ unsigned int cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    for (uint64_t i = threadIdx.x; i < sz; i += blockDim.x) {
-        sid_t v = edges[list_off + i];
-        uint64_t idx = (uint64_t)v - type_base;
-        uint16_t t = (idx < type_n) ? type_of[idx] : 0;
-        if ((sid_t)t == cval) {
-            unsigned p = atomicAdd(&cnt, 1u);
-            out[p] = v;
-        }
-        // multi-type entities (t==0xFFFF) would need the probe path; the
-        // host only routes here when the store has no such entities
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        d_state[S_NROWS] = cnt;
-        d_state[S_ERR] = 0;
-        for (int i = 0; i < S_WORDS; i++) h_pin[i] = d_state[i];
-        for (int i = 0; i < CAT_COUNT; i++) h_pin[8 + i] = d_stats[i];
-        atomicAdd((unsigned long long *)&d_stats[CAT_FILTER],
-                  (unsigned long long)(sz * 6 + cnt * 4));
-    }
-}
-
-// batched light queries: ONE launch executes a whole window of
-// light2-shaped queries (const_to_unknown + rdf:type filter), one
-// wavefront-sized workgroup per query.  This is the engine-side answer
-// to the reference proxy's in-flight window (proxy.hpp:477-525): at
-// 1024 in-flight light queries the bottleneck is kernel DISPATCH rate
-// (~10us/launch), so the scheduler packs the window into one grid.
-struct light_desc {
-    uint64_t off;      // edge-list offset of the c2u constant
-    uint64_t sz;       // edge-list length
-    uint64_t out_off;  // this query's region in the shared out buffer
-    uint32_t cval;     // rdf:type filter constant
-    uint32_t pad;
-};
-
-static const int LBLOCK = 64;  // one wavefront per query
-
-__global__ void k_light_batch(const sid_t *__restrict__ edges,
-                              const light_desc *__restrict__ descs,
-                              const uint16_t *__restrict__ type_of,
-                              uint64_t type_base, uint64_t type_n,
-                              sid_t *__restrict__ out,
-                              uint64_t *__restrict__ d_counts,
-                              uint64_t *__restrict__ d_stats)
-{
-    const light_desc d = descs[blockIdx.x];
-    __shared__ unsigned int cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    sid_t *qout = out + d.out_off;
-    for (uint64_t i = threadIdx.x; i < d.sz; i += blockDim.x) {
-        sid_t v = edges[d.off + i];
-        uint64_t idx = (uint64_t)v - type_base;
-        uint16_t t = (idx < type_n) ? type_of[idx] : 0;
-        if ((sid_t)t == d.cval) {
-            unsigned p = atomicAdd(&cnt, 1u);
-            qout[p] = v;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        d_counts[blockIdx.x] = cnt;
-        atomicAdd((unsigned long long *)&d_stats[CAT_FILTER],
-                  (unsigned long long)(d.sz * 6 + cnt * 4));
-    }
-}
-
-// ---------------------------------------------------------------------
-// batched whole-plan light queries: the LDS plan interpreter.
-//
-// The emulator's heavy templates (A4: 5 patterns, A6: 4 patterns,
-// proxy.hpp:391-545) have tiny intermediate tables (tens-hundreds of
-// rows) — per-pattern global kernels waste ~20 dispatches/query.  Here
-// ONE launch runs a window of same-template queries; each wavefront-
-// sized workgroup interprets the whole compiled plan with its binding
-// table staged in LDS (ping-pong buffers), probing the cluster hash in
-// global memory (64 independent probes in flight per wave).  A query
-// whose table outgrows LDS publishes WK_LP_OVERFLOW and the host
-// re-runs it on the general per-pattern path — results identical.
-// ---------------------------------------------------------------------
-enum { LOP_C2U = 0, LOP_TYPEOF, LOP_K2U, LOP_K2C, LOP_K2K };
-struct lop_t {
-    int32_t op, col, col2, dir;
-    uint32_t cval, pid;
-    uint64_t bucket_start, num_buckets;  // segment of (pid,dir)
-};
-struct lplan_t {
-    lop_t ops[8];
-    int32_t nops;
-};
-static const int LP_CAP = 6144;            // u32 slots per LDS buffer
-static const uint64_t WK_LP_OVERFLOW = ~0ull;
-
-__global__ void
-__launch_bounds__(64)
-k_plan_batch(const vertex_t *__restrict__ verts,
-             const sid_t *__restrict__ edges, const lplan_t lp,
-             const int64_t *__restrict__ consts,
-             const uint16_t *__restrict__ type_of, uint64_t type_base,
-             uint64_t type_n, uint64_t *__restrict__ d_counts,
-             uint64_t *__restrict__ d_stats)
-{
-    __shared__ sid_t bufA[LP_CAP], bufB[LP_CAP];
-    __shared__ unsigned s_n, s_cur, s_err;
-    __shared__ uint64_t s_eoff, s_esz, s_bytes;
-    sid_t *cur = bufA, *nxt = bufB;
-    int nc = 0;
-    uint64_t my_bytes = 0;
-    if (threadIdx.x == 0) { s_n = 0; s_err = 0; s_bytes = 0; }
-    __syncthreads();
-
-    for (int o = 0; o < lp.nops && !s_err; o++) {
-        const lop_t op = lp.ops[o];
-        if (op.op == LOP_C2U) {
-            if (threadIdx.x == 0) {
-                uint64_t key = key_pack((uint64_t)consts[blockIdx.x],
-                                        (uint64_t)op.pid, (uint64_t)op.dir);
-                s_eoff = 0; s_esz = 0;
-                if (op.num_buckets)
-                    probe_one(verts, op.bucket_start, op.num_buckets, key,
-                              s_eoff, s_esz);
-                if (s_esz > (uint64_t)LP_CAP) s_err = 1;
-                s_n = (unsigned)s_esz;
-                my_bytes += 148;
-            }
-            __syncthreads();
-            if (s_err) break;
-            for (unsigned i = threadIdx.x; i < s_n; i += blockDim.x)
-                cur[i] = edges[s_eoff + i];
-            if (threadIdx.x == 0) my_bytes += (uint64_t)s_n * 8;
-            nc = 1;
-            __syncthreads();
-        } else if (op.op == LOP_TYPEOF) {
-            if (threadIdx.x == 0) s_cur = 0;
-            __syncthreads();
-            for (unsigned r = threadIdx.x; r < s_n; r += blockDim.x) {
-                sid_t v = cur[r * nc + op.col];
-                uint64_t idx = (uint64_t)v - type_base;
-                uint16_t t = (idx < type_n) ? type_of[idx] : 0;
-                my_bytes += 6;
-                if ((sid_t)t == (sid_t)op.cval) {
-                    unsigned p = atomicAdd(&s_cur, 1u);
-                    for (int c = 0; c < nc; c++)
-                        nxt[p * nc + c] = cur[r * nc + c];
-                    my_bytes += (uint64_t)nc * 4;
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) s_n = s_cur;
-            sid_t *t_ = cur; cur = nxt; nxt = t_;
-            __syncthreads();
-        } else if (op.op == LOP_K2C || op.op == LOP_K2K) {
-            if (threadIdx.x == 0) s_cur = 0;
-            __syncthreads();
-            for (unsigned r = threadIdx.x; r < s_n; r += blockDim.x) {
-                sid_t v = cur[r * nc + op.col];
-                uint64_t eoff = 0, esz = 0;
-                uint64_t key = key_pack((uint64_t)v, (uint64_t)op.pid,
-                                        (uint64_t)op.dir);
-                if (op.num_buckets)
-                    probe_one(verts, op.bucket_start, op.num_buckets, key,
-                              eoff, esz);
-                sid_t tgt = (op.op == LOP_K2C) ? (sid_t)op.cval
-                                               : cur[r * nc + op.col2];
-                my_bytes += 148 + 32;  // probe + ~log2 bsearch lines
-                if (esz && bsearch_u32(edges + eoff, esz, tgt)) {
-                    unsigned p = atomicAdd(&s_cur, 1u);
-                    for (int c = 0; c < nc; c++)
-                        nxt[p * nc + c] = cur[r * nc + c];
-                    my_bytes += (uint64_t)nc * 4;
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) s_n = s_cur;
-            sid_t *t_ = cur; cur = nxt; nxt = t_;
-            __syncthreads();
-        } else {  // LOP_K2U
-            if (threadIdx.x == 0) s_cur = 0;
-            __syncthreads();
-            for (unsigned r = threadIdx.x; r < s_n; r += blockDim.x) {
-                sid_t v = cur[r * nc + op.col];
-                uint64_t eoff = 0, esz = 0;
-                uint64_t key = key_pack((uint64_t)v, (uint64_t)op.pid,
-                                        (uint64_t)op.dir);
-                if (op.num_buckets)
-                    probe_one(verts, op.bucket_start, op.num_buckets, key,
-                              eoff, esz);
-                my_bytes += 148;
-                unsigned base = atomicAdd(&s_cur, (unsigned)esz);
-                if (((uint64_t)base + esz) * (nc + 1) > (uint64_t)LP_CAP) {
-                    s_err = 1;
-                    continue;
-                }
-                for (uint64_t e = 0; e < esz; e++) {
-                    sid_t *dst = nxt + (base + e) * (nc + 1);
-                    for (int c = 0; c < nc; c++) dst[c] = cur[r * nc + c];
-                    dst[nc] = edges[eoff + e];
-                }
-                my_bytes += esz * (uint64_t)(nc + 1) * 4 + esz * 4;
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) s_n = s_cur;
-            sid_t *t_ = cur; cur = nxt; nxt = t_;
-            nc++;
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    atomicAdd((unsigned long long *)&s_bytes, (unsigned long long)my_bytes);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        d_counts[blockIdx.x] = s_err ? WK_LP_OVERFLOW : (uint64_t)s_n;
-        atomicAdd((unsigned long long *)&d_stats[CAT_FILTER],
-                  (unsigned long long)s_bytes);
-    }
-}
-
-// ---------------------------------------------------------------------
-// VERSATILE predicate-variable ops (sparql.hpp:556-744): one kernel
-// covers known/const_unknown_unknown (append p [, y] columns) and
-// known/const_unknown_const (keep one row per matching p).  Block per
-// input row; the row vid's predicate list comes from the dense vp CSR;
-// each predicate probes its own (pid,dir) segment via the device
-// segment table.  Appends use the global S_TOTAL cursor (k_commit
-// finalises; overflow -> S_ERR/S_REQ re-run like every other op).
-// ---------------------------------------------------------------------
-enum { VU_END_NEW = 0, VU_END_CONST = 1 };
-__global__ void k_vu(const vertex_t *__restrict__ verts,
-                     const sid_t *__restrict__ edges,
-                     const sid_t *__restrict__ in_tbl, int ncols, int col,
-                     sid_t const_start,
-                     const uint32_t *__restrict__ vp_off,
-                     const sid_t *__restrict__ vp_edges,
-                     uint64_t vp_base, uint64_t vp_n,
-                     const seg_t *__restrict__ segtab, uint32_t max_pid,
-                     int dir, int end_mode, sid_t cval,
-                     sid_t *__restrict__ out, int out_cols, uint64_t cap_rows,
-                     uint64_t *__restrict__ d_state,
-                     uint64_t *__restrict__ d_stats)
-{
-    const uint64_t nrows = (col >= 0) ? d_state[S_NROWS] : 1;
-    uint64_t bytes = 0;
-    for (uint64_t r = blockIdx.x; r < nrows; r += gridDim.x) {
-        sid_t vid = (col >= 0) ? in_tbl[r * ncols + col] : const_start;
-        uint64_t idx = (uint64_t)vid - vp_base;
-        if (idx >= vp_n) continue;
-        uint64_t plo = vp_off[idx], phi = vp_off[idx + 1];
-        bytes += 8;
-        for (uint64_t pi = plo + threadIdx.x; pi < phi; pi += blockDim.x) {
-            sid_t p = vp_edges[pi];
-            uint64_t eoff = 0, esz = 0;
-            if (p <= max_pid) {
-                const seg_t sg = segtab[p * 2 + dir];
-                if (sg.num_buckets)
-                    probe_one(verts, sg.bucket_start, sg.num_buckets,
-                              key_pack((uint64_t)vid, (uint64_t)p,
-                                       (uint64_t)dir),
-                              eoff, esz);
-            }
-            bytes += 4 + 148;
-            if (end_mode == VU_END_CONST) {
-                if (esz && bsearch_u32(edges + eoff, esz, cval)) {
-                    uint64_t pos = atomicAdd(
-                        (unsigned long long *)&d_state[S_TOTAL], 1ull);
-                    if (pos < cap_rows) {
-                        sid_t *dst = out + pos * out_cols;
-                        for (int c = 0; c < ncols; c++)
-                            dst[c] = in_tbl[r * ncols + c];
-                        dst[ncols] = p;
-                        bytes += (uint64_t)out_cols * 4;
-                    }
-                }
-            } else {
-                uint64_t pos = atomicAdd(
-                    (unsigned long long *)&d_state[S_TOTAL],
-                    (unsigned long long)esz);
-                for (uint64_t k = 0; k < esz && pos + k < cap_rows; k++) {
-                    sid_t *dst = out + (pos + k) * out_cols;
-                    for (int c = 0; c < ncols; c++)
-                        dst[c] = in_tbl[r * ncols + c];
-                    dst[ncols] = p;
-                    dst[ncols + 1] = edges[eoff + k];
-                }
-                bytes += esz * ((uint64_t)out_cols * 4 + 4);
-            }
-        }
-    }
-    if (bytes)
-        atomicAdd((unsigned long long *)&d_stats[CAT_EXPAND],
-                  (unsigned long long)bytes);
-}
-
-// ---------------------------------------------------------------------
-// OPTIONAL-mode operators (sparql.hpp:100-170, 316-375; BGP-only like
-// the reference, query.hpp:722-733): rows are never dropped — a row
-// whose pattern fails keeps BLANK_ID in every column first bound inside
-// the OPTIONAL group (blank_mask) and clears its matched flag.  This is
-// a correctness/coverage path (no LUBM/WatDiv benchmark uses OPTIONAL),
-// so the expansion uses a plain global append cursor.
-// ---------------------------------------------------------------------
-__global__ void k_filter_opt(const vertex_t *__restrict__ verts,
-                             const sid_t *__restrict__ edges,
-                             uint64_t bucket_start, uint64_t num_buckets,
-                             sid_t *__restrict__ tbl, int ncols, int col,
-                             uint32_t pid, int dir, int probe_mode, int col2,
-                             sid_t cval, uint64_t list_off, uint64_t list_sz,
-                             uint32_t blank_mask, uint8_t *__restrict__ flags,
-                             uint64_t *__restrict__ d_state,
-                             uint64_t *__restrict__ d_stats)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * (4 + 128 + 8 + 64));
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
-        sid_t v = tbl[r * ncols + col];
-        bool ok;
-        if (probe_mode == PM_LIST) {
-            ok = bsearch_u32(edges + list_off, list_sz, v);
-        } else {
-            uint64_t eoff = 0, esz = 0;
-            if (v != BLANK_ID && num_buckets)
-                probe_one(verts, bucket_start, num_buckets,
-                          key_pack((uint64_t)v, (uint64_t)pid, (uint64_t)dir),
-                          eoff, esz);
-            sid_t tgt = (probe_mode == PM_CONST) ? cval
-                                                 : tbl[r * ncols + col2];
-            ok = esz && tgt != BLANK_ID && bsearch_u32(edges + eoff, esz, tgt);
-        }
-        if (!ok) {
-            if (flags[r]) {
-                for (int c = 0; c < ncols; c++)
-                    if ((blank_mask >> c) & 1)
-                        tbl[r * ncols + c] = BLANK_ID;
-            }
-            flags[r] = 0;
-        }
-    }
-}
-
-__global__ void k_expand_opt(const vertex_t *__restrict__ verts,
-                             const sid_t *__restrict__ edges,
-                             const sid_t *__restrict__ tbl, int ncols,
-                             int col, uint32_t pid, int dir, int key_mode,
-                             uint64_t bucket_start, uint64_t num_buckets,
-                             const uint8_t *__restrict__ flags_in,
-                             uint8_t *__restrict__ flags_out,
-                             sid_t *__restrict__ out, uint64_t cap,
-                             uint64_t *__restrict__ d_state,
-                             uint64_t *__restrict__ d_stats)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    const int oc = ncols + 1;
-    count_bytes(d_stats, CAT_EXPAND, (uint64_t)nrows * (4 + 128 + 8));
-    // block-aggregated append (one global atomic per 256-row tile)
-    // replaces the round-1 per-row cursors — a single cursor word
-    // saturates at ~88 atomics/us (microarch row `dequeue`)
-    __shared__ unsigned long long s_base;
-    __shared__ uint64_t sh[SCAN_T];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < nrows;
-         base += stride) {
-        const int64_t r = base + threadIdx.x;
-        uint64_t eoff = 0, esz = 0, emit = 0;
-        uint8_t m = 0;
-        sid_t v = 0;
-        if (r < nrows) {
-            v = tbl[r * ncols + col];
-            m = flags_in[r];
-            if (m && v != BLANK_ID && num_buckets) {
-                uint64_t key = (key_mode == PK_NORMAL)
-                                   ? key_pack((uint64_t)v, (uint64_t)pid,
-                                              (uint64_t)dir)
-                                   : key_pack(0, (uint64_t)v, (uint64_t)dir);
-                probe_one(verts, bucket_start, num_buckets, key, eoff, esz);
-            }
-            // unmatched / blank / no edges: keep the row, BLANK new
-            // col; the matched flag survives unchanged
-            // (sparql.hpp:328-334, 352-356)
-            emit = (!m || v == BLANK_ID || esz == 0) ? 1 : esz;
-        }
-        sh[threadIdx.x] = emit;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        const uint64_t my_end = sh[threadIdx.x];
-        const uint64_t block_total = sh[SCAN_T - 1];
-        if (threadIdx.x == SCAN_T - 1)
-            s_base = block_total
-                         ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
-                                     (unsigned long long)block_total)
-                         : 0;
-        __syncthreads();
-        if (r < nrows) {
-            uint64_t pos = s_base + my_end - emit;
-            if (!m || v == BLANK_ID || esz == 0) {
-                if (pos < cap) {
-                    sid_t *dst = out + pos * oc;
-                    for (int c = 0; c < ncols; c++) dst[c] = tbl[r * ncols + c];
-                    dst[ncols] = BLANK_ID;
-                    flags_out[pos] = m;
-                }
-            } else {
-                for (uint64_t k = 0; k < esz && pos + k < cap; k++) {
-                    sid_t *dst = out + (pos + k) * oc;
-                    for (int c = 0; c < ncols; c++) dst[c] = tbl[r * ncols + c];
-                    dst[ncols] = edges[eoff + k];
-                    flags_out[pos + k] = 1;
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// OPTIMISTIC functional k2u: used ONLY inside captured graphs for
-// steps whose warm pass dropped no rows (store is immutable, so the
-// observation holds for replays; a miss at runtime still flips S_ERR
-// via k_commit_map and the caller falls back to the safe path).  The
-// 1:1 write needs no scan/compaction and coalesces perfectly.
-template <int NC>
-__global__ void k_expand_fn_map(const sid_t *__restrict__ tbl,
-                                const fnpage_t *__restrict__ fn_pg,
-                                const sid_t *__restrict__ fn_vals,
-                                uint64_t fn_base, uint64_t fn_n, int col,
-                                int use_typeof,
-                                const uint64_t *__restrict__ tbm,
-                                const uint16_t *__restrict__ type_of,
-                                uint64_t type_base, uint64_t type_n,
-                                sid_t fcval, int commit_mode,
-                                uint64_t *__restrict__ d_state,
-                                uint64_t *__restrict__ d_stats,
-                                sid_t *__restrict__ out)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    constexpr int oc = NC + 1;
-    count_bytes(d_stats, CAT_EXPAND,
-                (uint64_t)nrows * (24 + (use_typeof ? 1 : 0) + oc * 4));
-    uint32_t miss = 0;
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
-        sid_t v = tbl[r * NC + col];
-        sid_t tv = fn_lookup(fn_pg, fn_vals, fn_base, fn_n, v);
-        bool ok = tv != 0;
-        if (ok && use_typeof) {
-            uint64_t tix = (uint64_t)tv - type_base;
-            if (tbm) {
-                ok = tix < type_n && ((tbm[tix >> 6] >> (tix & 63)) & 1);
-            } else {
-                uint16_t t = (tix < type_n) ? type_of[tix] : 0;
-                ok = ((sid_t)t == fcval);  // 0xFFFF never matches ->
-                                           // counts as miss -> fallback
-            }
-        }
-        miss += ok ? 0u : 1u;
-        sid_t *dst = out + r * oc;
-#pragma unroll
-        for (int c = 0; c < NC; c++) dst[c] = tbl[r * NC + c];
-        dst[NC] = tv;
-    }
-    if (miss)
-        atomicAdd((unsigned long long *)&d_state[S_OVF],
-                  (unsigned long long)miss);
-    commit_tail(d_state, 0, commit_mode);
-}
-
-// ---------------------------------------------------------------------
-// xGMI peer-probe small-table step — the reference's one-sided in-place
-// remote read (gstore.hpp:260-338), gated by the fork-join threshold
-// (need_fork_join, sparql.hpp:802-814, Global::rdma_threshold=300): a
-// binding table below the threshold probes the OWNER rank's HBM store
-// directly through HIP-IPC peer mappings over xGMI instead of shipping
-// rows with an all-to-allv.  ONE workgroup — tables are tiny, so the
-// block-local scan keeps compaction exact with zero global atomics.
-struct wk_peer_desc {
-    const vertex_t *verts;
-    const sid_t *edges;
-    const uint16_t *type_of;
-    uint64_t type_base, type_n;
-};
-struct segtab8 { uint64_t bs[8]; uint64_t nb[8]; };  // per-rank (pid,dir) segment
-
-__global__ void k_peer_step(const wk_peer_desc *__restrict__ peers, int nsrv,
-                            segtab8 seg,
-                            const sid_t *__restrict__ tbl, int ncols, int col,
-                            uint32_t pid, int dir, int pmode, int col2,
-                            sid_t cval, uint64_t cap,
-                            uint64_t *__restrict__ d_state,
-                            uint64_t *__restrict__ d_stats,
-                            sid_t *__restrict__ out)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 + 128 + 8));
-    __shared__ uint64_t sh[SCAN_T];
-    const int oc = pmode == PM_SIZE ? ncols + 1 : ncols;
-    uint64_t carry = 0;
-    for (int64_t base = 0; base < nrows; base += SCAN_T) {
-        const int64_t r = base + threadIdx.x;
-        uint64_t deg = 0;  // rows to emit (expand: fanout; filter: 0/1)
-        const sid_t *el = nullptr;
-        if (r < nrows) {
-            sid_t v = tbl[r * ncols + col];
-            int owner = (int)(v % (sid_t)nsrv);
-            const wk_peer_desc P = peers[owner];
-            bool resolved = false;
-            // `?v rdf:type CONST` via the owner's dense side index;
-            // multi-type (0xFFFF) falls through to the owner probe of
-            // the same [v|TYPE|OUT] segment
-            if (pmode == PM_CONST && pid == TYPE_ID && dir == DIR_OUT &&
-                P.type_of) {
-                uint64_t tix = (uint64_t)v - P.type_base;
-                uint16_t t = (tix < P.type_n) ? P.type_of[tix] : 0;
-                if (t != 0xFFFF) {
-                    deg = ((sid_t)t == cval) ? 1 : 0;
-                    resolved = true;
-                }
-            }
-            if (!resolved && seg.nb[owner]) {
-                uint64_t eoff = 0, esz = 0;
-                probe_one(P.verts, seg.bs[owner], seg.nb[owner],
-                          key_pack(v, pid, (uint64_t)dir), eoff, esz);
-                if (pmode == PM_SIZE) {
-                    deg = esz;
-                    el = P.edges + eoff;
-                } else if (esz) {
-                    sid_t tgt = pmode == PM_CONST ? cval
-                                                  : tbl[r * ncols + col2];
-                    deg = bsearch_u32(P.edges + eoff, esz, tgt) ? 1 : 0;
-                }
-            }
-        }
-        sh[threadIdx.x] = deg;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        uint64_t pos = carry + sh[threadIdx.x] - deg;
-        carry += sh[SCAN_T - 1];
-        __syncthreads();
-        if (r < nrows && deg) {
-            if (pmode == PM_SIZE) {
-                for (uint64_t k = 0; k < deg; k++) {
-                    uint64_t dst = pos + k;
-                    if (dst >= cap) break;
-                    sid_t *d = out + dst * oc;
-                    for (int c = 0; c < ncols; c++) d[c] = tbl[r * ncols + c];
-                    d[ncols] = el[k];
-                }
-            } else if (pos < cap) {
-                sid_t *d = out + pos * oc;
-                for (int c = 0; c < ncols; c++) d[c] = tbl[r * ncols + c];
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {  // single block: commit inline (k_commit)
-        uint64_t t = carry;
-        if (t > cap) {
-            d_state[S_ERR] = 1;
-            d_state[S_REQ] = max(d_state[S_REQ], t);
-            t = cap;
-        }
-        d_state[S_NROWS] = t;
-        d_state[S_TOTAL] = 0;
-        d_state[S_OVF] = 0;
-    }
-}
-
-// verify-fused expansion epilogue: any inline-typeof miss (S_DONE)
-// flips S_ERR so the replay is discarded and the safe path re-runs
-__global__ void k_verify_commit(uint64_t *__restrict__ d_state) {
-    if (d_state[S_DONE]) {
-        d_state[S_ERR] = 1;
-        d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
-        d_state[S_DONE] = 0;
-    }
-}
-
-// commit for the optimistic map: row count unchanged; any miss flags
-// S_ERR so the replay result is discarded and the safe path re-runs
-__global__ void k_commit_map(uint64_t *__restrict__ d_state) {
-    if (d_state[S_OVF]) {
-        d_state[S_ERR] = 1;
-        d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
-    }
-    d_state[S_TOTAL] = 0;
-    d_state[S_OVF] = 0;
-}
-
-__global__ void k_zero_words(uint64_t *p, int n) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
-}
+#include "wk_kernels_common.h"
+#include "wk_kernels_expand.h"
+#include "wk_kernels_filter.h"
+#include "wk_kernels_batch.h"
 
 // ---------------------------------------------------------------------
 // engine
@@ -2561,6 +783,135 @@ static int32_t sync_state_grow(wk_engine *e) {
 // expansion dispatch, specialised on the input column count so the row
 // copy unrolls/vectorises (runtime-indexed local arrays spill to scratch
 // — cdna_hip_programming.md §5.4 rule 20)
+//
+// with_ncols is the ONE place a runtime column count (1..8) picks a
+// compile-time NC: it calls f(std::integral_constant<int, NC>{}).  The
+// `default -> 8` arm is safe because wk_engine_begin_query rejects
+// nvars > 8, so no binding table is ever wider than 8 columns.
+template <class F>
+static void with_ncols(int ncols, F &&f) {
+    switch (ncols) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+
+// ---- pieces shared by the step_* operators ---------------------------
+
+// warm-pass hint: pattern `step` dropped no rows (consulted ONLY while
+// capturing a graph)
+static bool hint_nodrop(const wk_engine *e, int step) {
+    return e->capturing && step < (int)e->capture_hint.size() &&
+           e->capture_hint[step];
+}
+
+// Const type id of a following `?o rdf:type CONST` pattern on this
+// step's output variable o, or 0.  Pattern shape only: every caller adds
+// its own guards (nsrv == 1, hints, !hinting, bitmap present, ...).
+static sid_t typeof_lookahead(const wk_engine *e, ssid_t o) {
+    if (e->step + 1 >= (int)e->pats.size()) return 0;
+    const wk_pattern_t &nx = e->pats[e->step + 1];
+    if (nx.subject == o && nx.predicate == (ssid_t)TYPE_ID &&
+        nx.direction == DIR_OUT && nx.object > 0)
+        return (sid_t)nx.object;
+    return 0;
+}
+
+// per-type membership bitmap of a type id (null = not built)
+static const uint64_t *type_bitmap(const wk_engine *e, sid_t type_id) {
+    return (e->gs && (size_t)type_id < e->gs->d_tbm.size())
+               ? e->gs->d_tbm[type_id]
+               : nullptr;
+}
+
+// End-of-step bookkeeping: bind new_var (a variable, < 0; 0 = none) to
+// the appended column, set the column count and the host row bound, and
+// consume `consumed` patterns.  finish_step is for steps that wrote the
+// OTHER table buffer (flip, drop any zero-copy view);
+// finish_step_in_place is for the steps that leave the current table
+// where it is (OPTIONAL filter, verify-only filter, absent segment).
+static void finish_step_in_place(wk_engine *e, ssid_t new_var, int out_cols,
+                                 int64_t bound, int consumed) {
+    if (new_var < 0) e->v2c[-(new_var + 1)] = e->ncols;
+    e->ncols = out_cols;
+    e->bound = bound;
+    e->step += consumed;
+}
+static void finish_step(wk_engine *e, ssid_t new_var, int out_cols,
+                        int64_t bound, int consumed) {
+    finish_step_in_place(e, new_var, out_cols, bound, consumed);
+    e->cur ^= 1;
+    e->tbl_view = nullptr;
+}
+
+static void launch_commit(wk_engine *e) {
+    hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, e->stream, e->d_state,
+                       (uint64_t)e->cap_rows);
+}
+static void launch_commit_map(wk_engine *e) {
+    hipLaunchKernelGGL(k_commit_map, dim3(1), dim3(1), 0, e->stream,
+                       e->d_state);
+}
+
+// fparams of a fixed-list membership filter (c2k/i2k): keep the rows
+// whose `col` value is in the sorted list edges[off, off+sz)
+static fparams fparams_list(const wk_engine *e, const sid_t *edges,
+                            const sid_t *cur_tbl, int col, int dir,
+                            uint64_t off, uint64_t sz) {
+    return fparams{e->d_verts, edges, 0, 1, cur_tbl, e->ncols, col, 0u,
+                   dir, PK_NORMAL, PM_LIST, 0, 0u, off, sz, e->d_type_of,
+                   0, 0, 0, nullptr, nullptr, nullptr, 0, 0, 0};
+}
+static void launch_filter_tpr(wk_engine *e, const fparams &P, int verify_only,
+                              sid_t *out_tbl) {
+    hipLaunchKernelGGL(k_filter_tpr, dim3(grid_for(e->bound)), dim3(BLOCK), 0,
+                       e->stream, P, verify_only, e->d_state, e->d_stats,
+                       out_tbl);
+}
+
+static void launch_scan_mid(wk_engine *e, int G) {
+    hipLaunchKernelGGL(k_scan_mid, dim3(1), dim3(SCAN_T), 0, e->stream,
+                       (uint64_t *)e->bsums.p, G, (uint64_t)e->cap_rows,
+                       e->d_state);
+}
+// Front half of a scan-pipeline step: gather() launches the 1:1 kernel
+// that fills cnt, then k_scan_local + k_scan_mid turn the counts into
+// output positions (k_scan_mid also commits the step).  `timed`
+// attributes gather + scan_local to CAT_PROBE and scan_mid to CAT_SCAN
+// (the CSR paths); the fn pipeline passes false because its caller
+// times the whole chain as CAT_EXPAND.
+template <class Gather>
+static void launch_gather_scan(wk_engine *e, int G, bool timed,
+                               Gather &&gather) {
+    auto front = [&] {
+        gather();
+        hipLaunchKernelGGL(k_scan_local, dim3(G), dim3(SCAN_T), 0, e->stream,
+                           (const uint32_t *)e->cnt.p, e->d_state,
+                           (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p);
+    };
+    if (!timed) {
+        front();
+        launch_scan_mid(e, G);
+        return;
+    }
+    {
+        TIME_BEGIN(e);
+        front();
+        TIME_END(e, CAT_PROBE);
+    }
+    {
+        TIME_BEGIN(e);
+        launch_scan_mid(e, G);
+        TIME_END(e, CAT_SCAN);
+    }
+}
+
 struct expand_verify {  // fused no-drop typeof check (captured graphs)
     const uint64_t *tbm = nullptr;
     const uint16_t *type_of = nullptr;
@@ -2583,7 +934,7 @@ static void launch_expand_t(wk_engine *e, const sid_t *cur_tbl, sid_t *out_tbl,
                        cur_tbl, e->ncols, e->d_edges, (uint64_t *)e->eoff.p,
                        (uint32_t *)e->cnt.p, (uint64_t *)e->prefix.p,
                        (uint64_t *)e->bsums.p, G, e->d_state,
-                       (uint64_t)e->cap_rows, /*commit*/ 0,
+                       (uint64_t)e->cap_rows,
                        (uint32_t *)e->ovf.p, vf.tbm, vf.type_of, vf.base,
                        vf.n, vf.cval, vf.on, out_tbl);
     if (vf.on)
@@ -2592,65 +943,28 @@ static void launch_expand_t(wk_engine *e, const sid_t *cur_tbl, sid_t *out_tbl,
 }
 
 template <int NC>
-static void launch_expand_filter_t(wk_engine *e, const sid_t *cur_tbl,
-                                   sid_t *out_tbl, sid_t fcval,
-                                   const seg_t *fseg) {
-    hipLaunchKernelGGL(k_expand_filter<NC>, dim3(grid_for(e->bound)), dim3(BLOCK),
-                       0, e->stream, cur_tbl, e->ncols, e->d_edges,
-                       (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p, e->d_state,
-                       (uint64_t)e->cap_rows, e->d_stats, (uint32_t *)e->ovf.p,
-                       fcval, e->d_type_of, e->st->type_base, e->st->type_n,
-                       e->d_verts, fseg->bucket_start, fseg->num_buckets, out_tbl);
-    hipLaunchKernelGGL(k_expand_filter_big<NC>, dim3(512), dim3(BLOCK), 0,
-                       e->stream, cur_tbl, e->ncols, e->d_edges,
-                       (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p, e->d_state,
-                       (uint64_t)e->cap_rows, (uint32_t *)e->ovf.p, fcval,
-                       e->d_type_of, e->st->type_base, e->st->type_n,
-                       e->d_verts, fseg->bucket_start, fseg->num_buckets, out_tbl);
-}
-
-static void launch_expand_filter(wk_engine *e, const sid_t *cur_tbl,
-                                 sid_t *out_tbl, sid_t fcval, const seg_t *fseg) {
-    switch (e->ncols) {
-    case 1: launch_expand_filter_t<1>(e, cur_tbl, out_tbl, fcval, fseg); break;
-    case 2: launch_expand_filter_t<2>(e, cur_tbl, out_tbl, fcval, fseg); break;
-    case 3: launch_expand_filter_t<3>(e, cur_tbl, out_tbl, fcval, fseg); break;
-    case 4: launch_expand_filter_t<4>(e, cur_tbl, out_tbl, fcval, fseg); break;
-    case 5: launch_expand_filter_t<5>(e, cur_tbl, out_tbl, fcval, fseg); break;
-    case 6: launch_expand_filter_t<6>(e, cur_tbl, out_tbl, fcval, fseg); break;
-    case 7: launch_expand_filter_t<7>(e, cur_tbl, out_tbl, fcval, fseg); break;
-    default: launch_expand_filter_t<8>(e, cur_tbl, out_tbl, fcval, fseg); break;
-    }
-}
-
-template <int NC>
 static void launch_expand_fn_t(wk_engine *e, const sid_t *cur_tbl,
                                sid_t *out_tbl, const fnpage_t *d_pg,
                                const sid_t *d_vals, int col,
                                bool fuse, sid_t fcval, const seg_t *fseg) {
-    const uint64_t *tbm =
-        (fuse && e->gs && (size_t)fcval < e->gs->d_tbm.size())
-            ? e->gs->d_tbm[fcval]
-            : nullptr;
+    const uint64_t *tbm = fuse ? type_bitmap(e, fcval) : nullptr;
     // atomic-free pipeline: 1:1 gather of resolved objects (+0/1
     // counts), deterministic positions via the chunked scan, then a
     // barrier-free scatter.  A per-tile cursor atomic costs ~23 us per
     // 2048-block round (single-word ~88 atomics/us) and held every
     // in-kernel-aggregation variant of this step at a flat ~107 us.
     const int G = scan_grid(e->bound);
-    hipLaunchKernelGGL(k_fn_gather, dim3(grid_for(e->bound)), dim3(BLOCK),
-                       0, e->stream, cur_tbl, e->ncols, d_pg, d_vals,
-                       e->st->fn_base, e->st->fn_n, col, fuse ? 1 : 0, fcval,
-                       e->d_type_of, tbm, e->st->type_base, e->st->type_n,
-                       e->d_verts, e->d_edges, fseg ? fseg->bucket_start : 0,
-                       fseg ? fseg->num_buckets : 0, e->d_state, e->d_stats,
-                       (sid_t *)e->ovf.p, (uint32_t *)e->cnt.p);
-    hipLaunchKernelGGL(k_scan_local, dim3(G), dim3(SCAN_T), 0, e->stream,
-                       (const uint32_t *)e->cnt.p, e->d_state,
-                       (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p);
-    hipLaunchKernelGGL(k_scan_mid, dim3(1), dim3(SCAN_T), 0, e->stream,
-                       (uint64_t *)e->bsums.p, G, (uint64_t)e->cap_rows,
-                       e->d_state);
+    launch_gather_scan(e, G, /*timed*/ false, [&] {
+        hipLaunchKernelGGL(k_fn_gather, dim3(grid_for(e->bound)), dim3(BLOCK),
+                           0, e->stream, cur_tbl, e->ncols, d_pg, d_vals,
+                           e->st->fn_base, e->st->fn_n, col, fuse ? 1 : 0,
+                           fcval, e->d_type_of, tbm, e->st->type_base,
+                           e->st->type_n, e->d_verts, e->d_edges,
+                           fseg ? fseg->bucket_start : 0,
+                           fseg ? fseg->num_buckets : 0, e->d_state,
+                           e->d_stats, (sid_t *)e->ovf.p,
+                           (uint32_t *)e->cnt.p);
+    });
     hipLaunchKernelGGL(k_fn_scatter<NC>, dim3(grid_for(e->bound)), dim3(BLOCK),
                        0, e->stream, cur_tbl, (const sid_t *)e->ovf.p,
                        (const uint32_t *)e->cnt.p, (const uint64_t *)e->prefix.p,
@@ -2663,47 +977,30 @@ static void launch_expand_fn_map_t(wk_engine *e, const sid_t *cur_tbl,
                                    sid_t *out_tbl, const fnpage_t *d_pg,
                                    const sid_t *d_vals,
                                    int col, bool fuse, sid_t fcval) {
-    const uint64_t *tbm =
-        (fuse && e->gs && (size_t)fcval < e->gs->d_tbm.size())
-            ? e->gs->d_tbm[fcval]
-            : nullptr;
+    const uint64_t *tbm = fuse ? type_bitmap(e, fcval) : nullptr;
     hipLaunchKernelGGL(k_expand_fn_map<NC>, dim3(grid_for(e->bound)),
                        dim3(BLOCK), 0, e->stream, cur_tbl, d_pg, d_vals,
                        e->st->fn_base, e->st->fn_n, col, fuse ? 1 : 0, tbm,
                        e->d_type_of, e->st->type_base, e->st->type_n, fcval,
-                       /*commit*/ 0, e->d_state, e->d_stats, out_tbl);
+                       e->d_state, e->d_stats, out_tbl);
 }
 
 static void launch_expand_fn_map(wk_engine *e, const sid_t *cur_tbl,
                                  sid_t *out_tbl, const fnpage_t *d_pg,
                                  const sid_t *d_vals, int col,
                                  bool fuse, sid_t fcval) {
-    switch (e->ncols) {
-    case 1: launch_expand_fn_map_t<1>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval); break;
-    case 2: launch_expand_fn_map_t<2>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval); break;
-    case 3: launch_expand_fn_map_t<3>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval); break;
-    case 4: launch_expand_fn_map_t<4>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval); break;
-    case 5: launch_expand_fn_map_t<5>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval); break;
-    case 6: launch_expand_fn_map_t<6>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval); break;
-    case 7: launch_expand_fn_map_t<7>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval); break;
-    default: launch_expand_fn_map_t<8>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval); break;
-    }
+    with_ncols(e->ncols, [&](auto nc) {
+        launch_expand_fn_map_t<decltype(nc)::value>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval);
+    });
 }
 
 static void launch_expand_fn(wk_engine *e, const sid_t *cur_tbl,
                              sid_t *out_tbl, const fnpage_t *d_pg,
                              const sid_t *d_vals, int col,
                              bool fuse, sid_t fcval, const seg_t *fseg) {
-    switch (e->ncols) {
-    case 1: launch_expand_fn_t<1>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg); break;
-    case 2: launch_expand_fn_t<2>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg); break;
-    case 3: launch_expand_fn_t<3>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg); break;
-    case 4: launch_expand_fn_t<4>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg); break;
-    case 5: launch_expand_fn_t<5>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg); break;
-    case 6: launch_expand_fn_t<6>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg); break;
-    case 7: launch_expand_fn_t<7>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg); break;
-    default: launch_expand_fn_t<8>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg); break;
-    }
+    with_ncols(e->ncols, [&](auto nc) {
+        launch_expand_fn_t<decltype(nc)::value>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg);
+    });
 }
 
 template <int NC>
@@ -2726,30 +1023,16 @@ static void launch_expand_tf_t(wk_engine *e, const sid_t *cur_tbl,
 
 static void launch_expand_tf(wk_engine *e, const sid_t *cur_tbl,
                              sid_t *out_tbl, int G, const uint64_t *tbm) {
-    switch (e->ncols) {
-    case 1: launch_expand_tf_t<1>(e, cur_tbl, out_tbl, G, tbm); break;
-    case 2: launch_expand_tf_t<2>(e, cur_tbl, out_tbl, G, tbm); break;
-    case 3: launch_expand_tf_t<3>(e, cur_tbl, out_tbl, G, tbm); break;
-    case 4: launch_expand_tf_t<4>(e, cur_tbl, out_tbl, G, tbm); break;
-    case 5: launch_expand_tf_t<5>(e, cur_tbl, out_tbl, G, tbm); break;
-    case 6: launch_expand_tf_t<6>(e, cur_tbl, out_tbl, G, tbm); break;
-    case 7: launch_expand_tf_t<7>(e, cur_tbl, out_tbl, G, tbm); break;
-    default: launch_expand_tf_t<8>(e, cur_tbl, out_tbl, G, tbm); break;
-    }
+    with_ncols(e->ncols, [&](auto nc) {
+        launch_expand_tf_t<decltype(nc)::value>(e, cur_tbl, out_tbl, G, tbm);
+    });
 }
 
 static void launch_expand(wk_engine *e, const sid_t *cur_tbl, sid_t *out_tbl,
                           int G, const expand_verify &vf) {
-    switch (e->ncols) {
-    case 1: launch_expand_t<1>(e, cur_tbl, out_tbl, G, vf); break;
-    case 2: launch_expand_t<2>(e, cur_tbl, out_tbl, G, vf); break;
-    case 3: launch_expand_t<3>(e, cur_tbl, out_tbl, G, vf); break;
-    case 4: launch_expand_t<4>(e, cur_tbl, out_tbl, G, vf); break;
-    case 5: launch_expand_t<5>(e, cur_tbl, out_tbl, G, vf); break;
-    case 6: launch_expand_t<6>(e, cur_tbl, out_tbl, G, vf); break;
-    case 7: launch_expand_t<7>(e, cur_tbl, out_tbl, G, vf); break;
-    default: launch_expand_t<8>(e, cur_tbl, out_tbl, G, vf); break;
-    }
+    with_ncols(e->ncols, [&](auto nc) {
+        launch_expand_t<decltype(nc)::value>(e, cur_tbl, out_tbl, G, vf);
+    });
 }
 
 // Remote (xGMI peer-probe) variant of one pattern: small tables probe
@@ -2796,15 +1079,422 @@ static int32_t exec_pattern_remote(wk_engine *e) {
                        e->d_state, e->d_stats, out_tbl);
     TIME_END(e, CAT_PROBE);
     // commit inlined in k_peer_step (single block)
-    if (pmode == PM_SIZE) {
-        e->v2c[-(o + 1)] = e->ncols;
-        e->ncols += 1;
-        e->bound = e->cap_rows;
-    }
-    e->cur ^= 1;
-    e->tbl_view = nullptr;
-    e->step++;
+    if (pmode == PM_SIZE)
+        finish_step(e, o, e->ncols + 1, e->cap_rows, 1);
+    else
+        finish_step(e, 0, e->ncols, e->bound, 1);
     return WK_OK;
+}
+
+// ---------------------------------------------------------------------
+// One step_* function per operator; exec_pattern (below) validates,
+// picks the operator and calls it.  step_ctx carries the pattern and
+// the two table buffers; col/key_mode/seg are filled for known-start
+// steps only.
+// ---------------------------------------------------------------------
+struct step_ctx {
+    ssid_t s, p, o;
+    int dir;
+    const sid_t *cur_tbl;  // current table (may be a zero-copy view)
+    sid_t *out_tbl;        // the other buffer
+    int col = -1;          // column of the known subject
+    int key_mode = PK_NORMAL;
+    const seg_t *seg = nullptr;  // segment of the fixed (pid,dir)
+};
+
+// ---- OPTIONAL-mode dispatch (sparql.hpp:100-170,316-375) ----
+static int32_t step_optional(wk_engine *e, const step_ctx &c) {
+    const wk_store *st = e->st;
+    const ssid_t s = c.s, p = c.p, o = c.o;
+    const int dir = c.dir;
+    if (p < 0) return WK_ERR_PLAN;  // BGP-only, like the reference
+    const bool cstart = s >= 0;
+    if (cstart && is_tpid(s)) return WK_ERR_PLAN;  // no index starts
+    int ocol = cstart ? e->var2col(o) : e->var2col(s);
+    if (ocol < 0 && cstart) return WK_ERR_PLAN;  // c2u inside OPTIONAL
+    if (!cstart && e->var2col(s) < 0) return WK_ERR_PLAN;
+    const int ostat = e->var_stat(o);
+    const seg_t *oseg = st->seg_of((uint64_t)1 << NBITS_IDX, (uint64_t)p, dir);
+    int okey_mode = PK_NORMAL;
+    if (!cstart && ostat == 0 && (sid_t)p == TYPE_ID && dir == DIR_IN) {
+        okey_mode = PK_INDEX;
+        oseg = &st->iseg[DIR_IN];
+    }
+    uint64_t bs = oseg ? oseg->bucket_start : 0;
+    uint64_t nb = oseg ? oseg->num_buckets : 0;
+    if (cstart || ostat != 0) {
+        // filter-style: in place, flags transition, no compaction
+        uint64_t loff = 0, lsz = 0;
+        int pm;
+        int fcol, fcol2 = 0;
+        sid_t fcval = 0;
+        if (cstart) {  // const_to_known (sparql.hpp:138-186, OPTIONAL)
+            const sid_t *ptr =
+                store_get(*st, (uint64_t)s, (uint64_t)p, dir, &lsz);
+            loff = ptr ? (uint64_t)(ptr - st->edges.data()) : 0;
+            pm = PM_LIST;
+            fcol = ocol;
+        } else {
+            pm = (ostat == 2) ? PM_CONST : PM_COL;
+            fcol = e->var2col(s);
+            fcol2 = (ostat == 1) ? e->var2col(o) : 0;
+            fcval = (ostat == 2) ? (sid_t)o : 0;
+        }
+        TIME_BEGIN(e);
+        // exec_pattern materialised any view: the owned buffer IS current
+        hipLaunchKernelGGL(k_filter_opt, dim3(grid_for(e->bound)),
+                           dim3(BLOCK), 0, e->stream, e->d_verts,
+                           e->d_edges, bs, nb,
+                           (sid_t *)e->tbl[e->cur].p, e->ncols, fcol,
+                           (uint32_t)p, dir, pm, fcol2, fcval, loff, lsz,
+                           e->opt_mask, (uint8_t *)e->oflag[e->ocur].p,
+                           e->d_state, e->d_stats);
+        TIME_END(e, CAT_FILTER);
+        // nrows unchanged; no commit (S_NROWS stays), no table flip
+        finish_step_in_place(e, 0, e->ncols, e->bound, 1);
+        return WK_OK;
+    }
+    // known_to_unknown inside OPTIONAL: append column, keep rows
+    const int oc = e->ncols + 1;
+    if (oc > e->cap_cols) return WK_ERR_STATE;
+    TIME_BEGIN(e);
+    hipLaunchKernelGGL(k_expand_opt, dim3(grid_for(e->bound)),
+                       dim3(BLOCK), 0, e->stream, e->d_verts, e->d_edges,
+                       c.cur_tbl, e->ncols, e->var2col(s), (uint32_t)p, dir,
+                       okey_mode, bs, nb,
+                       (const uint8_t *)e->oflag[e->ocur].p,
+                       (uint8_t *)e->oflag[e->ocur ^ 1].p, c.out_tbl,
+                       (uint64_t)e->cap_rows, e->d_state, e->d_stats);
+    TIME_END(e, CAT_EXPAND);
+    launch_commit(e);
+    e->opt_mask |= 1u << e->ncols;
+    e->ocur ^= 1;
+    finish_step(e, o, oc, e->cap_rows, 1);
+    return WK_OK;
+}
+
+// ---- VERSATILE: predicate variable (sparql.hpp:556-744) ----
+static int32_t step_versatile(wk_engine *e, const step_ctx &c) {
+    const wk_store *st = e->st;
+    const ssid_t s = c.s, p = c.p, o = c.o;
+    const int dir = c.dir;
+    if (!st->vp_n || !e->gs || !e->gs->d_segtab) return WK_ERR_PLAN;
+    int pvar = -(p + 1);
+    if (pvar >= e->nvars || e->v2c[pvar] >= 0) return WK_ERR_PLAN;
+    const bool cstart = s >= 0;
+    int col = -1;
+    if (cstart) {
+        // const_unknown_* must be the first pattern (sparql.hpp:719)
+        if (e->ncols != 0 || is_tpid(s)) return WK_ERR_PLAN;
+    } else {
+        col = e->var2col(s);
+        if (col < 0) return WK_ERR_PLAN;
+    }
+    const int ostat = e->var_stat(o);
+    if (ostat == 1) return WK_ERR_PLAN;  // known_unknown_known: absent
+                                         // in the reference too
+    const int end_mode = (ostat == 2) ? VU_END_CONST : VU_END_NEW;
+    const int oc = e->ncols + (end_mode == VU_END_CONST ? 1 : 2);
+    if (oc > e->cap_cols) return WK_ERR_STATE;
+    int G = (int)std::min<int64_t>(std::max<int64_t>(e->bound, 1), 4096);
+    if (cstart) G = 1;
+    TIME_BEGIN(e);
+    hipLaunchKernelGGL(k_vu, dim3(G), dim3(64), 0, e->stream,
+                       e->d_verts, e->d_edges, c.cur_tbl, e->ncols, col,
+                       cstart ? (sid_t)s : 0,
+                       e->gs->d_vp_off[dir], e->gs->d_vp_edges[dir],
+                       st->vp_base, st->vp_n, e->gs->d_segtab,
+                       st->max_pid, dir, end_mode,
+                       ostat == 2 ? (sid_t)o : 0, c.out_tbl, oc,
+                       (uint64_t)e->cap_rows, e->d_state, e->d_stats);
+    TIME_END(e, CAT_EXPAND);
+    launch_commit(e);
+    // two appended columns: the predicate, then (VU_END_NEW) the object
+    e->v2c[pvar] = e->ncols;
+    if (end_mode == VU_END_NEW) e->v2c[-(o + 1)] = e->ncols + 1;
+    finish_step(e, 0, oc, e->cap_rows, 1);
+    return WK_OK;
+}
+
+// ---- step 0: index start (query.hpp:660-682) / const start ----
+// index_to_unknown (sparql.hpp:194-231) or const_to_unknown (:238-285):
+// a host-probed list becomes a 1-col table
+static int32_t step_start(wk_engine *e, const step_ctx &c, bool index_start) {
+    const wk_store *st = e->st;
+    if (!index_start && e->ncols != 0) return WK_ERR_PLAN;
+    uint64_t sz = 0;
+    const sid_t *ptr =
+        index_start ? store_get(*st, 0, (uint64_t)c.s, c.dir, &sz)
+                    : store_get(*st, (uint64_t)c.s, (uint64_t)c.p, c.dir, &sz);
+    uint64_t off = ptr ? (uint64_t)(ptr - st->edges.data()) : 0;
+    int32_t rc = grow_caps(e, (int64_t)sz, e->nvars);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream, e->d_state,
+                       sz);
+    // the new table REPLACES whatever was current: ?o is column 0
+    e->v2c[-(c.o + 1)] = 0;
+    finish_step(e, 0, 1, (int64_t)sz, 1);
+    // zero-copy: the 1-col table IS the stored edge list (immutable)
+    e->tbl_view = sz ? e->d_edges + off : nullptr;
+    e->nrows = (int64_t)sz;
+    return WK_OK;
+}
+
+// ---- const_to_known (sparql.hpp:138-186): fixed-list membership ----
+static int32_t step_const_to_known(wk_engine *e, const step_ctx &c) {
+    const wk_store *st = e->st;
+    int col = e->var2col(c.o);
+    if (col < 0) return WK_ERR_PLAN;
+    uint64_t sz = 0;
+    const sid_t *ptr =
+        store_get(*st, (uint64_t)c.s, (uint64_t)c.p, c.dir, &sz);
+    uint64_t off = ptr ? (uint64_t)(ptr - st->edges.data()) : 0;
+    TIME_BEGIN(e);
+    launch_filter_tpr(e, fparams_list(e, e->d_edges, c.cur_tbl, col, c.dir,
+                                      off, sz), 0, c.out_tbl);
+    TIME_END(e, CAT_FILTER);
+    launch_commit(e);
+    finish_step(e, 0, e->ncols, e->bound, 1);
+    return WK_OK;
+}
+
+// known start, segment absent: every probe misses -> empty table, left
+// in place (no kernel wrote the other buffer)
+static int32_t step_absent_segment(wk_engine *e, const step_ctx &c,
+                                   int ostat) {
+    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream, e->d_state, 0);
+    e->nrows = 0;
+    if (ostat == 0)
+        finish_step_in_place(e, c.o, e->ncols + 1, 0, 1);
+    else
+        finish_step_in_place(e, 0, e->ncols, 0, 1);
+    return WK_OK;
+}
+
+// ---- known_to_const / known_to_known filter (sparql.hpp:416-476) ----
+static int32_t step_filter(wk_engine *e, const step_ctx &c, int ostat) {
+    const wk_store *st = e->st;
+    const ssid_t p = c.p, o = c.o;
+    const int dir = c.dir;
+    int pmode = (ostat == 2) ? PM_CONST : PM_COL;
+    int col2 = (ostat == 1) ? e->var2col(o) : 0;
+    sid_t cval = (ostat == 2) ? (sid_t)o : 0;
+    // identity-verified filter: the graph build's warm pass saw this
+    // step keep every row, so the captured graph runs a read-only
+    // verification (typeof/membership checks on every row, misses ->
+    // S_ERR -> replay discarded + safe fallback) with no compaction
+    // write and no table flip (q7's COURSE filter: 86us -> ~40us)
+    const bool verify_only = hint_nodrop(e, e->step);
+    TIME_BEGIN(e);
+    int use_typeof = (pmode == PM_CONST && (sid_t)p == TYPE_ID &&
+                      dir == DIR_OUT && c.key_mode == PK_NORMAL &&
+                      e->d_type_of != nullptr)
+                         ? 1 : 0;
+    const uint64_t *d_tbm = use_typeof ? type_bitmap(e, cval) : nullptr;
+    // functional predicate: row's single object replaces the probe.
+    // If only the REVERSED direction is functional, k2k checks
+    // fn[other col] == col (fn_swap); k2c resolves the single edge
+    // endpoint HOST-side and becomes a pure equality compare (PM_EQ).
+    const fnpage_t *d_pg = nullptr;
+    const sid_t *d_vals = nullptr;
+    int fn_swap = 0;
+    if (!use_typeof && c.key_mode == PK_NORMAL && e->gs &&
+        !e->gs->d_fn_pages.empty() && wk_fn_dispatch()) {
+        d_pg = e->gs->d_fn_pages[(size_t)p * 2 + dir];
+        d_vals = e->gs->d_fn_vals[(size_t)p * 2 + dir];
+        // the REVERSED map keys the non-routed endpoint, which is
+        // only complete on a single-partition store (the forward map
+        // is partitioned on the same axis as the probe routing)
+        if (!d_pg && st->nsrv == 1) {
+            const fnpage_t *rpg = e->gs->d_fn_pages[(size_t)p * 2 + (dir ^ 1)];
+            if (rpg && pmode == PM_COL) {
+                d_pg = rpg;
+                d_vals = e->gs->d_fn_vals[(size_t)p * 2 + (dir ^ 1)];
+                fn_swap = 1;
+            } else if (rpg && pmode == PM_CONST) {
+                // host lookup: the const's single neighbour
+                sid_t tv = st->fn_get((size_t)p * 2 + (dir ^ 1), cval);
+                pmode = PM_EQ;
+                cval = tv;  // 0 never matches a vid -> empty result
+            }
+        }
+    }
+    fparams P{e->d_verts, e->d_edges, c.seg->bucket_start,
+              c.seg->num_buckets, c.cur_tbl, e->ncols, c.col, (uint32_t)p,
+              dir, c.key_mode, pmode, col2, cval, 0, 0, e->d_type_of,
+              st->type_base, st->type_n, use_typeof, d_tbm,
+              d_pg, d_vals, st->fn_base, st->fn_n, fn_swap};
+    // one-pass ballot filter: measured FASTER than the
+    // flags+scan+scatter pipeline at suite keep-rates (graph-q1
+    // 205 -> 264 us with the pipeline: the extra passes cost more
+    // than the per-tile cursor atomics they remove)
+    launch_filter_tpr(e, P, verify_only ? 1 : 0, c.out_tbl);
+    TIME_END(e, CAT_FILTER);
+    if (verify_only) {
+        // no rows written: the table stays where it is
+        launch_commit_map(e);
+        finish_step_in_place(e, 0, e->ncols, e->bound, 1);
+        return WK_OK;
+    }
+    launch_commit(e);
+    finish_step(e, 0, e->ncols, e->bound, 1);
+    return WK_OK;
+}
+
+// known_to_unknown over a FUNCTIONAL predicate (deg==1 rank-compressed
+// map): probe+scan+expand collapse to a page+value gather pair +
+// compacted append, with an optional fused typeof filter on the new
+// column.  Output rows <= input rows, so no capacity risk; e->bound is
+// unchanged.
+static int32_t step_k2u_fn(wk_engine *e, const step_ctx &c,
+                           const fnpage_t *d_pg, const sid_t *d_vals) {
+    // this look-ahead needs the dense type_of and the [v|TYPE|OUT]
+    // segment (k_fn_gather's multi-type probe); unlike step_k2u's
+    // it is NOT disabled while hinting
+    sid_t fcval = (e->d_type_of && e->st->nsrv == 1) ? typeof_lookahead(e, c.o)
+                                                     : 0;
+    const seg_t *fseg =
+        fcval ? e->st->seg_of((uint64_t)1 << NBITS_IDX, TYPE_ID, DIR_OUT)
+              : nullptr;
+    if (!(fseg && fseg->num_buckets)) fcval = 0;
+    const bool fuse = fcval != 0;
+    // optimistic 1:1 map: only while capturing a graph, and only
+    // when the build's warm pass saw this step drop no rows
+    const bool opt = hint_nodrop(e, e->step);
+    TIME_BEGIN(e);
+    if (opt)
+        launch_expand_fn_map(e, c.cur_tbl, c.out_tbl, d_pg, d_vals, c.col,
+                             fuse, fcval);
+    else
+        launch_expand_fn(e, c.cur_tbl, c.out_tbl, d_pg, d_vals, c.col,
+                         fuse, fcval, fseg);
+    TIME_END(e, CAT_EXPAND);
+    // the scan pipeline committed in k_scan_mid; the 1:1 map did not
+    if (opt) launch_commit_map(e);
+    finish_step(e, c.o, e->ncols + 1, e->bound, fuse ? 2 : 1);
+    return WK_OK;
+}
+
+// EXACT fused `k2u + ?v rdf:type CONST` compaction over the CSR index
+// (nothing optimistic: output == expansion-then-filter output): the CSR
+// walk counts type-bitmap-passing values, the scan yields exact
+// positions, the writer re-walks and emits only those.
+static int32_t step_k2u_tf(wk_engine *e, const step_ctx &c,
+                           const fnpage_t *c_pg, const uint64_t *tf_tbm) {
+    const wk_store *st = e->st;
+    const int G = scan_grid(e->bound);
+    launch_gather_scan(e, G, /*timed*/ true, [&] {
+        hipLaunchKernelGGL(k_csr_gather_tf, dim3(grid_for(e->bound)),
+                           dim3(BLOCK), 0, e->stream, c.cur_tbl, e->ncols,
+                           c.col, c_pg,
+                           e->gs->d_csr_entries[(size_t)c.p * 2 + c.dir],
+                           st->fn_base, st->fn_n, e->d_edges, tf_tbm,
+                           st->type_base, st->type_n, e->d_state, e->d_stats,
+                           (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p);
+    });
+    {
+        TIME_BEGIN(e);
+        launch_expand_tf(e, c.cur_tbl, c.out_tbl, G, tf_tbm);
+        TIME_END(e, CAT_EXPAND);
+    }
+    // consumed the typeof filter pattern too
+    finish_step(e, c.o, e->ncols + 1, e->cap_rows, 2);
+    return WK_OK;
+}
+
+// classic known_to_unknown: CSR gather (24-B probes) or fused cluster-
+// hash probe+scan -> cross-block scan -> input-centric expansion (+
+// big-row wave pass)
+static int32_t step_k2u_classic(wk_engine *e, const step_ctx &c,
+                                const fnpage_t *c_pg) {
+    const wk_store *st = e->st;
+    const int G = scan_grid(e->bound);
+    if (c_pg) {
+        launch_gather_scan(e, G, /*timed*/ true, [&] {
+            hipLaunchKernelGGL(k_csr_gather, dim3(grid_for(e->bound)),
+                               dim3(BLOCK), 0, e->stream, c.cur_tbl, e->ncols,
+                               c.col, c_pg,
+                               e->gs->d_csr_entries[(size_t)c.p * 2 + c.dir],
+                               st->fn_base, st->fn_n, e->d_state, e->d_stats,
+                               (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p);
+        });
+    } else {
+        {
+            TIME_BEGIN(e);
+            hipLaunchKernelGGL(k_probe_scan, dim3(G), dim3(SCAN_T), 0,
+                               e->stream, e->d_verts, c.cur_tbl, e->ncols,
+                               c.col, (uint32_t)c.p, c.dir, c.key_mode,
+                               c.seg->bucket_start, c.seg->num_buckets,
+                               e->d_state, e->d_stats, (uint64_t *)e->eoff.p,
+                               (uint32_t *)e->cnt.p, (uint64_t *)e->prefix.p,
+                               (uint64_t *)e->bsums.p);
+            TIME_END(e, CAT_PROBE);
+        }
+        {
+            TIME_BEGIN(e);
+            launch_scan_mid(e, G);
+            TIME_END(e, CAT_SCAN);
+        }
+    }
+    // verify-fused no-drop typeof on the NEW column (captured graphs
+    // only, warm-pass hint — same guard scheme as fn_map): the
+    // separate full-table verify pass collapses into the expansion's
+    // write loop + a 1-thread epilogue.  Unlike the other two
+    // look-aheads this one accepts the dense type_of OR the bitmap.
+    expand_verify vf;
+    if (hint_nodrop(e, e->step + 1) && st->nsrv == 1)
+        vf.cval = typeof_lookahead(e, c.o);
+    if (vf.cval) {
+        vf.base = st->type_base;
+        vf.n = st->type_n;
+        vf.tbm = type_bitmap(e, vf.cval);
+        vf.type_of = e->d_type_of;
+        if (vf.tbm || vf.type_of) vf.on = 1;
+    }
+    {
+        TIME_BEGIN(e);
+        launch_expand(e, c.cur_tbl, c.out_tbl, G, vf);
+        TIME_END(e, CAT_EXPAND);
+    }
+    // fan-out unknown until a sync point; a fused verify consumed the
+    // filter pattern too
+    finish_step(e, c.o, e->ncols + 1, e->cap_rows, vf.on ? 2 : 1);
+    return WK_OK;
+}
+
+// known_to_unknown: pick the pipeline (fn map, exact typeof-fused CSR,
+// classic)
+static int32_t step_k2u(wk_engine *e, const step_ctx &c) {
+    const wk_store *st = e->st;
+    if (e->ncols + 1 > e->cap_cols) return WK_ERR_STATE;  // begin_query sizes cap_cols
+    const size_t w_seg = (size_t)c.p * 2 + c.dir;
+    // side indexes key [vid|pid|dir] only; WK_FN_DISPATCH=0 routes
+    // around both (diagnostic / roofline probe of the classic pipeline)
+    const bool side = c.key_mode == PK_NORMAL && e->gs && wk_fn_dispatch();
+    if (side && !e->gs->d_fn_pages.empty() && e->gs->d_fn_pages[w_seg])
+        return step_k2u_fn(e, c, e->gs->d_fn_pages[w_seg],
+                           e->gs->d_fn_vals[w_seg]);
+    // CSR side index (rank-compressed, non-functional segments); the
+    // cluster-hash probe remains the fallback
+    const fnpage_t *c_pg = (side && !e->gs->d_csr_pages.empty())
+                               ? e->gs->d_csr_pages[w_seg]
+                               : nullptr;
+    // The typeof-fused CSR pipeline is skipped when the capture hint
+    // says the filter drops nothing (the verify-fused classic expansion
+    // is cheaper there), while hinting (per-pattern counts needed), and
+    // on hub-heavy segments: its count pass walks a row's whole edge
+    // list in one thread, so a 10^5-edge hub key would serialize (fine
+    // for LUBM/WatDiv leaf predicates, avg deg <= ~8)
+    const bool tf_deg_ok =
+        w_seg < st->seg_keys.size() && st->seg_keys[w_seg] &&
+        st->seg_edges[w_seg] / st->seg_keys[w_seg] <= 32;
+    if (c_pg && tf_deg_ok && st->nsrv == 1 && !e->hinting &&
+        !hint_nodrop(e, e->step + 1)) {
+        const sid_t t = typeof_lookahead(e, c.o);
+        const uint64_t *tf_tbm = t ? type_bitmap(e, t) : nullptr;
+        if (tf_tbm) return step_k2u_tf(e, c, c_pg, tf_tbm);
+    }
+    return step_k2u_classic(e, c, c_pg);
 }
 
 // Run one pattern — dispatch per sparql.hpp:1016-1058.  Fully async: row
@@ -2814,528 +1504,38 @@ static int32_t exec_pattern(wk_engine *e) {
     if (e->step == e->remote_step_idx) return exec_pattern_remote(e);
     const wk_store *st = e->st;
     const wk_pattern_t pat = e->pats[e->step];
-    const ssid_t s = pat.subject, p = pat.predicate, o = pat.object;
-    const int dir = pat.direction;
     // OPT-group kernels write the current table IN PLACE (BLANK fill):
     // a zero-copy i2u view must be materialised first
     if (e->opt_mode && e->tbl_view) {
         int32_t rcm = materialize_view(e);
         if (rcm) return rcm;
     }
-    const sid_t *cur_tbl = cur_table(e);
-    sid_t *out_tbl = (sid_t *)e->tbl[e->cur ^ 1].p;
+    step_ctx c{pat.subject, pat.predicate, pat.object, pat.direction,
+               cur_table(e), (sid_t *)e->tbl[e->cur ^ 1].p};
+    if (e->opt_mode) return step_optional(e, c);
+    if (c.p < 0) return step_versatile(e, c);
 
-    // ---- OPTIONAL-mode dispatch (sparql.hpp:100-170,316-375) ----
-    if (e->opt_mode) {
-        if (p < 0) return WK_ERR_PLAN;  // BGP-only, like the reference
-        const bool cstart = s >= 0;
-        if (cstart && is_tpid(s)) return WK_ERR_PLAN;  // no index starts
-        int ocol = cstart ? e->var2col(o) : e->var2col(s);
-        if (ocol < 0 && cstart) return WK_ERR_PLAN;  // c2u inside OPTIONAL
-        if (!cstart && e->var2col(s) < 0) return WK_ERR_PLAN;
-        const int ostat = (o >= 0) ? 2 : (e->var2col(o) >= 0 ? 1 : 0);
-        const seg_t *oseg = st->seg_of((uint64_t)1 << NBITS_IDX,
-                                       (uint64_t)p, dir);
-        int okey_mode = PK_NORMAL;
-        if (!cstart && ostat == 0 && (sid_t)p == TYPE_ID && dir == DIR_IN) {
-            okey_mode = PK_INDEX;
-            oseg = &st->iseg[DIR_IN];
-        }
-        uint64_t bs = oseg ? oseg->bucket_start : 0;
-        uint64_t nb = oseg ? oseg->num_buckets : 0;
-        if (cstart || ostat != 0) {
-            // filter-style: in place, flags transition, no compaction
-            uint64_t loff = 0, lsz = 0;
-            int pm;
-            int fcol, fcol2 = 0;
-            sid_t fcval = 0;
-            if (cstart) {  // const_to_known (sparql.hpp:138-186, OPTIONAL)
-                const sid_t *ptr =
-                    store_get(*st, (uint64_t)s, (uint64_t)p, dir, &lsz);
-                loff = ptr ? (uint64_t)(ptr - st->edges.data()) : 0;
-                pm = PM_LIST;
-                fcol = ocol;
-            } else {
-                pm = (ostat == 2) ? PM_CONST : PM_COL;
-                fcol = e->var2col(s);
-                fcol2 = (ostat == 1) ? e->var2col(o) : 0;
-                fcval = (ostat == 2) ? (sid_t)o : 0;
-            }
-            TIME_BEGIN(e);
-            // view was materialised above: the owned buffer IS current
-            hipLaunchKernelGGL(k_filter_opt, dim3(grid_for(e->bound)),
-                               dim3(BLOCK), 0, e->stream, e->d_verts,
-                               e->d_edges, bs, nb,
-                               (sid_t *)e->tbl[e->cur].p, e->ncols, fcol,
-                               (uint32_t)p, dir, pm, fcol2, fcval, loff, lsz,
-                               e->opt_mask, (uint8_t *)e->oflag[e->ocur].p,
-                               e->d_state, e->d_stats);
-            TIME_END(e, CAT_FILTER);
-            // nrows unchanged; no commit (S_NROWS stays), no table flip
-            e->step++;
-            return WK_OK;
-        }
-        // known_to_unknown inside OPTIONAL: append column, keep rows
-        const int oc = e->ncols + 1;
-        if (oc > e->cap_cols) return WK_ERR_STATE;
-        TIME_BEGIN(e);
-        hipLaunchKernelGGL(k_expand_opt, dim3(grid_for(e->bound)),
-                           dim3(BLOCK), 0, e->stream, e->d_verts, e->d_edges,
-                           cur_tbl, e->ncols, e->var2col(s), (uint32_t)p, dir,
-                           okey_mode, bs, nb,
-                           (const uint8_t *)e->oflag[e->ocur].p,
-                           (uint8_t *)e->oflag[e->ocur ^ 1].p, out_tbl,
-                           (uint64_t)e->cap_rows, e->d_state, e->d_stats);
-        TIME_END(e, CAT_EXPAND);
-        hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, e->stream,
-                           e->d_state, (uint64_t)e->cap_rows);
-        e->v2c[-(o + 1)] = e->ncols;
-        e->opt_mask |= 1u << e->ncols;
-        e->ncols = oc;
-        e->cur ^= 1;
-        e->tbl_view = nullptr;
-        e->ocur ^= 1;
-        e->bound = e->cap_rows;
-        e->step++;
-        return WK_OK;
-    }
-
-    // ---- VERSATILE: predicate variable (sparql.hpp:556-744) ----
-    if (p < 0) {
-        if (!st->vp_n || !e->gs || !e->gs->d_segtab) return WK_ERR_PLAN;
-        int pvar = -(p + 1);
-        if (pvar >= e->nvars || e->v2c[pvar] >= 0) return WK_ERR_PLAN;
-        const bool cstart = s >= 0;
-        int col = -1;
-        if (cstart) {
-            // const_unknown_* must be the first pattern (sparql.hpp:719)
-            if (e->ncols != 0 || is_tpid(s)) return WK_ERR_PLAN;
-        } else {
-            col = e->var2col(s);
-            if (col < 0) return WK_ERR_PLAN;
-        }
-        const int ostat = (o >= 0) ? 2 : (e->var2col(o) >= 0 ? 1 : 0);
-        if (ostat == 1) return WK_ERR_PLAN;  // known_unknown_known: absent
-                                             // in the reference too
-        const int end_mode = (ostat == 2) ? VU_END_CONST : VU_END_NEW;
-        const int oc = e->ncols + (end_mode == VU_END_CONST ? 1 : 2);
-        if (oc > e->cap_cols) return WK_ERR_STATE;
-        int G = (int)std::min<int64_t>(std::max<int64_t>(e->bound, 1), 4096);
-        if (cstart) G = 1;
-        TIME_BEGIN(e);
-        hipLaunchKernelGGL(k_vu, dim3(G), dim3(64), 0, e->stream,
-                           e->d_verts, e->d_edges, cur_tbl, e->ncols, col,
-                           cstart ? (sid_t)s : 0,
-                           e->gs->d_vp_off[dir], e->gs->d_vp_edges[dir],
-                           st->vp_base, st->vp_n, e->gs->d_segtab,
-                           st->max_pid, dir, end_mode,
-                           ostat == 2 ? (sid_t)o : 0, out_tbl, oc,
-                           (uint64_t)e->cap_rows, e->d_state, e->d_stats);
-        TIME_END(e, CAT_EXPAND);
-        hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, e->stream,
-                           e->d_state, (uint64_t)e->cap_rows);
-        e->v2c[pvar] = e->ncols;
-        if (end_mode == VU_END_NEW) e->v2c[-(o + 1)] = e->ncols + 1;
-        e->ncols = oc;
-        e->cur ^= 1;
-        e->tbl_view = nullptr;
-        e->bound = e->cap_rows;
-        e->step++;
-        return WK_OK;
-    }
-
-    // ---- step 0: index start (query.hpp:660-682) / const start ----
-    const bool index_start = (e->step == 0 && s >= 0 && is_tpid(s));
-    if (index_start || (s >= 0 && o < 0 && e->var2col(o) < 0)) {
-        // index_to_unknown (sparql.hpp:194-231) or const_to_unknown
-        // (:238-285): materialise a host-probed list as a 1-col table
-        if (!index_start && e->ncols != 0) return WK_ERR_PLAN;
-        uint64_t sz = 0;
-        const sid_t *ptr = index_start ? store_get(*st, 0, (uint64_t)s, dir, &sz)
-                                       : store_get(*st, (uint64_t)s, (uint64_t)p, dir, &sz);
-        uint64_t off = ptr ? (uint64_t)(ptr - st->edges.data()) : 0;
-        int32_t rc = grow_caps(e, (int64_t)sz, e->nvars);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream, e->d_state,
-                           sz);
-        // zero-copy: the 1-col table IS the stored edge list (immutable)
-        e->cur ^= 1;
-        e->tbl_view = sz ? e->d_edges + off : nullptr;
-        e->nrows = (int64_t)sz;
-        e->bound = (int64_t)sz;
-        e->ncols = 1;
-        e->v2c[-(o + 1)] = 0;
-        e->step++;
-        return WK_OK;
-    }
-
-    // ---- const_to_known (sparql.hpp:138-186): fixed-list membership ----
-    if (s >= 0) {
-        int col = e->var2col(o);
-        if (col < 0) return WK_ERR_PLAN;
-        uint64_t sz = 0;
-        const sid_t *ptr = store_get(*st, (uint64_t)s, (uint64_t)p, dir, &sz);
-        uint64_t off = ptr ? (uint64_t)(ptr - st->edges.data()) : 0;
-        TIME_BEGIN(e);
-        fparams P{e->d_verts, e->d_edges, 0, 1, cur_tbl, e->ncols, col, 0u,
-                  dir, PK_NORMAL, PM_LIST, 0, 0u, off, sz, e->d_type_of,
-                  0, 0, 0, nullptr, nullptr, nullptr, 0, 0, 0};
-        hipLaunchKernelGGL(k_filter_tpr, dim3(grid_for(e->bound)), dim3(BLOCK),
-                           0, e->stream, P, 0, /*commit*/ 0, 0,
-                           e->d_state, e->d_stats, out_tbl);
-        TIME_END(e, CAT_FILTER);
-        hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, e->stream, e->d_state,
-                           (uint64_t)e->cap_rows);
-        e->cur ^= 1;
-        e->tbl_view = nullptr;
-        e->step++;
-        return WK_OK;
-    }
+    const bool index_start = (e->step == 0 && c.s >= 0 && is_tpid(c.s));
+    if (index_start || (c.s >= 0 && c.o < 0 && e->var2col(c.o) < 0))
+        return step_start(e, c, index_start);
+    if (c.s >= 0) return step_const_to_known(e, c);
 
     // ---- known start ----
-    int col = e->var2col(s);
-    if (col < 0) return WK_ERR_PLAN;  // UNKNOWN start: invalid plan (sparql.hpp:1044-1049)
-
+    c.col = e->var2col(c.s);
+    if (c.col < 0) return WK_ERR_PLAN;  // UNKNOWN start: invalid plan (sparql.hpp:1044-1049)
     // segment of the fixed (pid,dir); known_to_unknown's TYPE_ID/IN case
     // probes the index segment with per-row type keys (sparql.hpp:340-343)
-    int key_mode = PK_NORMAL;
-    const seg_t *seg;
-    if ((sid_t)p == TYPE_ID && dir == DIR_IN) {
-        key_mode = PK_INDEX;
-        seg = &st->iseg[DIR_IN];
+    if ((sid_t)c.p == TYPE_ID && c.dir == DIR_IN) {
+        c.key_mode = PK_INDEX;
+        c.seg = &st->iseg[DIR_IN];
     } else {
-        seg = st->seg_of((uint64_t)1 << NBITS_IDX, (uint64_t)p, dir);
+        c.seg = st->seg_of((uint64_t)1 << NBITS_IDX, (uint64_t)c.p, c.dir);
     }
-
-    const int ostat = (o >= 0) ? 2 : (e->var2col(o) >= 0 ? 1 : 0);
-    if (!seg || seg->num_buckets == 0) {
-        // segment absent: every probe misses -> empty table
-        hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream, e->d_state, 0);
-        e->nrows = 0;
-        e->bound = 0;
-        if (ostat == 0) {
-            e->v2c[-(o + 1)] = e->ncols;
-            e->ncols += 1;
-        }
-        e->step++;
-        return WK_OK;
-    }
-
-    int pmode = (ostat == 0) ? PM_SIZE : (ostat == 2 ? PM_CONST : PM_COL);
-    int col2 = (ostat == 1) ? e->var2col(o) : 0;
-    sid_t cval = (ostat == 2) ? (sid_t)o : 0;
-    if (pmode != PM_SIZE) {
-        // identity-verified filter: the graph build's warm pass saw this
-        // step keep every row, so the captured graph runs a read-only
-        // verification (typeof/membership checks on every row, misses ->
-        // S_ERR -> replay discarded + safe fallback) with no compaction
-        // write and no table flip (q7's COURSE filter: 86us -> ~40us)
-        const bool verify_only =
-            e->capturing && e->step < (int)e->capture_hint.size() &&
-            e->capture_hint[e->step];
-        TIME_BEGIN(e);
-        int use_typeof = (pmode == PM_CONST && (sid_t)p == TYPE_ID &&
-                          dir == DIR_OUT && key_mode == PK_NORMAL &&
-                          e->d_type_of != nullptr)
-                             ? 1 : 0;
-        const uint64_t *d_tbm =
-            (use_typeof && e->gs && (size_t)cval < e->gs->d_tbm.size())
-                ? e->gs->d_tbm[cval]
-                : nullptr;
-        // functional predicate: row's single object replaces the probe.
-        // If only the REVERSED direction is functional, k2k checks
-        // fn[other col] == col (fn_swap); k2c resolves the single edge
-        // endpoint HOST-side and becomes a pure equality compare (PM_EQ).
-        const fnpage_t *d_pg = nullptr;
-        const sid_t *d_vals = nullptr;
-        int fn_swap = 0;
-        if (!use_typeof && key_mode == PK_NORMAL && e->gs &&
-            !e->gs->d_fn_pages.empty() && wk_fn_dispatch()) {
-            d_pg = e->gs->d_fn_pages[(size_t)p * 2 + dir];
-            d_vals = e->gs->d_fn_vals[(size_t)p * 2 + dir];
-            // the REVERSED map keys the non-routed endpoint, which is
-            // only complete on a single-partition store (the forward map
-            // is partitioned on the same axis as the probe routing)
-            if (!d_pg && st->nsrv == 1 &&
-                (pmode == PM_COL || pmode == PM_CONST)) {
-                const fnpage_t *rpg = e->gs->d_fn_pages[(size_t)p * 2 + (dir ^ 1)];
-                if (rpg && pmode == PM_COL) {
-                    d_pg = rpg;
-                    d_vals = e->gs->d_fn_vals[(size_t)p * 2 + (dir ^ 1)];
-                    fn_swap = 1;
-                } else if (rpg && pmode == PM_CONST) {
-                    // host lookup: the const's single neighbour
-                    sid_t tv = st->fn_get((size_t)p * 2 + (dir ^ 1), cval);
-                    pmode = PM_EQ;
-                    cval = tv;  // 0 never matches a vid -> empty result
-                }
-            }
-        }
-        fparams P{e->d_verts, e->d_edges, seg->bucket_start,
-                  seg->num_buckets, cur_tbl, e->ncols, col, (uint32_t)p,
-                  dir, key_mode, pmode, col2, cval, 0, 0, e->d_type_of,
-                  e->st->type_base, e->st->type_n, use_typeof, d_tbm,
-                  d_pg, d_vals, st->fn_base, st->fn_n, fn_swap};
-        // one-pass ballot filter: measured FASTER than the
-        // flags+scan+scatter pipeline at suite keep-rates (graph-q1
-        // 205 -> 264 us with the pipeline: the extra passes cost more
-        // than the per-tile cursor atomics they remove)
-        hipLaunchKernelGGL(k_filter_tpr, dim3(grid_for(e->bound)),
-                           dim3(BLOCK), 0, e->stream, P,
-                           verify_only ? 1 : 0, /*commit*/ 0, 0,
-                           e->d_state, e->d_stats, out_tbl);
-        TIME_END(e, CAT_FILTER);
-        if (verify_only) {
-            hipLaunchKernelGGL(k_commit_map, dim3(1), dim3(1), 0, e->stream,
-                               e->d_state);
-            e->step++;
-            return WK_OK;
-        }
-    } else {
-        // known_to_unknown: fused probe+scan -> cross-block scan ->
-        // input-centric expansion (+ big-row wave pass)
-        const int G = scan_grid(e->bound);
-        int oc = e->ncols + 1;
-        if (oc > e->cap_cols) return WK_ERR_STATE;  // begin_query sizes cap_cols
-
-        // FUNCTIONAL predicate (deg==1 rank-compressed map):
-        // probe+scan+expand collapse to a page+value gather pair +
-        // block-compacted append, with an optional fused typeof filter
-        // on the new column.  Output rows <= input rows, so no capacity
-        // risk; e->bound is unchanged.
-        const bool have_fn = key_mode == PK_NORMAL && e->gs &&
-                             !e->gs->d_fn_pages.empty() && wk_fn_dispatch() &&
-                             e->gs->d_fn_pages[(size_t)p * 2 + dir];
-        const fnpage_t *d_pg =
-            have_fn ? e->gs->d_fn_pages[(size_t)p * 2 + dir] : nullptr;
-        const sid_t *d_vals =
-            have_fn ? e->gs->d_fn_vals[(size_t)p * 2 + dir] : nullptr;
-        if (d_pg) {
-            bool fuse2 = false;
-            sid_t fcval2 = 0;
-            const seg_t *fseg2 = nullptr;
-            if (e->step + 1 < (int)e->pats.size() && e->d_type_of &&
-                e->st->nsrv == 1) {
-                const wk_pattern_t &nx = e->pats[e->step + 1];
-                if (nx.subject == o && nx.predicate == (ssid_t)TYPE_ID &&
-                    nx.direction == DIR_OUT && nx.object > 0) {
-                    fseg2 = st->seg_of((uint64_t)1 << NBITS_IDX, TYPE_ID,
-                                       DIR_OUT);
-                    if (fseg2 && fseg2->num_buckets) {
-                        fuse2 = true;
-                        fcval2 = (sid_t)nx.object;
-                    }
-                }
-            }
-            // optimistic 1:1 map: only while capturing a graph, and only
-            // when the build's warm pass saw this step drop no rows
-            const bool opt = e->capturing &&
-                             e->step < (int)e->capture_hint.size() &&
-                             e->capture_hint[e->step];
-            TIME_BEGIN(e);
-            if (opt)
-                launch_expand_fn_map(e, cur_tbl, out_tbl, d_pg, d_vals, col,
-                                     fuse2, fcval2);
-            else
-                launch_expand_fn(e, cur_tbl, out_tbl, d_pg, d_vals, col,
-                                 fuse2, fcval2, fseg2);
-            TIME_END(e, CAT_EXPAND);
-            if (opt)  // 1:1 map path: commit_map still needed
-                hipLaunchKernelGGL(k_commit_map, dim3(1), dim3(1), 0,
-                                   e->stream, e->d_state);
-            // scan-pipeline path: k_scan_mid committed already
-            e->v2c[-(o + 1)] = e->ncols;
-            e->ncols = oc;
-            e->cur ^= 1;
-            e->tbl_view = nullptr;
-            e->step += fuse2 ? 2 : 1;
-            return WK_OK;
-        }
-
-        // look-ahead: a `?v rdf:type CONST` filter on THIS k2u's output
-        // var fuses into the expansion (saves a full table pass)
-        bool fuse = false;
-        sid_t fcval = 0;
-        const seg_t *fseg = nullptr;
-        // fusion needs the NEW column's type info locally: only valid on a
-        // single-partition store (type_of covers local subjects only), and
-        // it consumes two plan steps (incompatible with the per-pattern
-        // distributed driver).  DEFAULT OFF: measured net-negative until
-        // the fused kernels get the filter's 4-row batching (the per-tile
-        // counter atomics and the wave-pass per-row atomics serialize —
-        // q7's advisor expansion went 150us -> 4.2ms).  WK_FUSE=1 enables
-        // for experiments; parity is tested either way.
-        static const bool fuse_enabled = [] {
-            const char *v = getenv("WK_FUSE");
-            return v && atoi(v);
-        }();
-        if (fuse_enabled && e->step + 1 < (int)e->pats.size() && e->d_type_of &&
-            e->st->nsrv == 1) {
-            const wk_pattern_t &nx = e->pats[e->step + 1];
-            if (nx.subject == o && nx.predicate == (ssid_t)TYPE_ID &&
-                nx.direction == DIR_OUT && nx.object > 0) {
-                fseg = st->seg_of((uint64_t)1 << NBITS_IDX, TYPE_ID, DIR_OUT);
-                if (fseg && fseg->num_buckets) {
-                    fuse = true;
-                    fcval = (sid_t)nx.object;
-                }
-            }
-        }
-        // CSR side index (rank-compressed, non-functional segments):
-        // 24-B probes via a barrier-free gather + chunked scan; the
-        // cluster-hash probe remains the fallback and the
-        // WK_FN_DISPATCH=0 diagnostic path
-        const fnpage_t *c_pg =
-            (key_mode == PK_NORMAL && e->gs && wk_fn_dispatch() &&
-             !e->gs->d_csr_pages.empty())
-                ? e->gs->d_csr_pages[(size_t)p * 2 + dir]
-                : nullptr;
-        // EXACT fused `k2u + ?v rdf:type CONST` compaction (nothing
-        // optimistic: output == expansion-then-filter output): the CSR
-        // walk counts type-bitmap-passing values, the scan yields exact
-        // positions, the writer re-walks and emits only those.  Skipped
-        // when the capture hint says the filter drops nothing (the
-        // verify-fused expansion above is cheaper there).
-        // skip hub-heavy segments: the count pass walks a row's whole
-        // edge list in one thread, so a 10^5-edge hub key would
-        // serialize (fine for LUBM/WatDiv leaf predicates, avg deg <=
-        // ~8; hub segments keep the classic split pipeline)
-        const size_t w_seg = (size_t)p * 2 + dir;
-        const bool tf_deg_ok =
-            w_seg < e->st->seg_keys.size() && e->st->seg_keys[w_seg] &&
-            e->st->seg_edges[w_seg] / e->st->seg_keys[w_seg] <= 32;
-        if (c_pg && tf_deg_ok && e->st->nsrv == 1 && e->gs && !e->hinting &&
-            e->step + 1 < (int)e->pats.size()) {
-            const wk_pattern_t &nx = e->pats[e->step + 1];
-            const bool nodrop = e->capturing &&
-                                e->step + 1 < (int)e->capture_hint.size() &&
-                                e->capture_hint[e->step + 1];
-            if (!nodrop && nx.subject == o &&
-                nx.predicate == (ssid_t)TYPE_ID &&
-                nx.direction == DIR_OUT && nx.object > 0 &&
-                (size_t)nx.object < e->gs->d_tbm.size() &&
-                e->gs->d_tbm[nx.object]) {
-                const uint64_t *tf_tbm = e->gs->d_tbm[nx.object];
-                TIME_BEGIN(e);
-                hipLaunchKernelGGL(k_csr_gather_tf, dim3(grid_for(e->bound)),
-                                   dim3(BLOCK), 0, e->stream, cur_tbl,
-                                   e->ncols, col, c_pg,
-                                   e->gs->d_csr_entries[(size_t)p * 2 + dir],
-                                   st->fn_base, st->fn_n, e->d_edges, tf_tbm,
-                                   e->st->type_base, e->st->type_n,
-                                   e->d_state, e->d_stats,
-                                   (uint64_t *)e->eoff.p,
-                                   (uint32_t *)e->cnt.p);
-                hipLaunchKernelGGL(k_scan_local, dim3(G), dim3(SCAN_T), 0,
-                                   e->stream, (const uint32_t *)e->cnt.p,
-                                   e->d_state, (uint64_t *)e->prefix.p,
-                                   (uint64_t *)e->bsums.p);
-                TIME_END(e, CAT_PROBE);
-                {
-                    TIME_BEGIN(e);
-                    hipLaunchKernelGGL(k_scan_mid, dim3(1), dim3(SCAN_T), 0,
-                                       e->stream, (uint64_t *)e->bsums.p, G,
-                                       (uint64_t)e->cap_rows, e->d_state);
-                    TIME_END(e, CAT_SCAN);
-                }
-                {
-                    TIME_BEGIN(e);
-                    launch_expand_tf(e, cur_tbl, out_tbl, G, tf_tbm);
-                    TIME_END(e, CAT_EXPAND);
-                }
-                e->v2c[-(o + 1)] = e->ncols;
-                e->ncols = oc;
-                e->bound = e->cap_rows;
-                e->cur ^= 1;
-                e->tbl_view = nullptr;
-                e->step += 2;  // consumed the typeof filter pattern
-                return WK_OK;
-            }
-        }
-        TIME_BEGIN(e);
-        if (c_pg) {
-            hipLaunchKernelGGL(k_csr_gather, dim3(grid_for(e->bound)),
-                               dim3(BLOCK), 0, e->stream, cur_tbl, e->ncols,
-                               col, c_pg,
-                               e->gs->d_csr_entries[(size_t)p * 2 + dir],
-                               st->fn_base, st->fn_n, e->d_state, e->d_stats,
-                               (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p);
-            hipLaunchKernelGGL(k_scan_local, dim3(G), dim3(SCAN_T), 0,
-                               e->stream, (const uint32_t *)e->cnt.p,
-                               e->d_state, (uint64_t *)e->prefix.p,
-                               (uint64_t *)e->bsums.p);
-        } else {
-            hipLaunchKernelGGL(k_probe_scan, dim3(G), dim3(SCAN_T), 0, e->stream,
-                               e->d_verts, cur_tbl, e->ncols, col, (uint32_t)p, dir,
-                               key_mode, seg->bucket_start, seg->num_buckets,
-                               e->d_state, e->d_stats, (uint64_t *)e->eoff.p,
-                               (uint32_t *)e->cnt.p, (uint64_t *)e->prefix.p,
-                               (uint64_t *)e->bsums.p);
-        }
-        TIME_END(e, CAT_PROBE);
-        if (fuse) {
-            {
-                TIME_BEGIN(e);
-                launch_expand_filter(e, cur_tbl, out_tbl, fcval, fseg);
-                TIME_END(e, CAT_EXPAND);
-            }
-            e->v2c[-(o + 1)] = e->ncols;
-            e->ncols = oc;
-            e->bound = e->cap_rows;
-            hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, e->stream,
-                               e->d_state, (uint64_t)e->cap_rows);
-            e->cur ^= 1;
-            e->tbl_view = nullptr;
-            e->step += 2;  // consumed the fused filter pattern too
-            return WK_OK;
-        }
-        {
-            TIME_BEGIN(e);
-            hipLaunchKernelGGL(k_scan_mid, dim3(1), dim3(SCAN_T), 0, e->stream,
-                               (uint64_t *)e->bsums.p, G,
-                               (uint64_t)e->cap_rows, e->d_state);
-            TIME_END(e, CAT_SCAN);
-        }
-        // verify-fused no-drop typeof on the NEW column (captured
-        // graphs only, warm-pass hint — same guard scheme as fn_map):
-        // the separate full-table verify pass collapses into the
-        // expansion's write loop + a 1-thread epilogue
-        expand_verify vf;
-        if (e->capturing && e->step + 1 < (int)e->pats.size() &&
-            e->step + 1 < (int)e->capture_hint.size() &&
-            e->capture_hint[e->step + 1] && e->st->nsrv == 1) {
-            const wk_pattern_t &nx = e->pats[e->step + 1];
-            if (nx.subject == o && nx.predicate == (ssid_t)TYPE_ID &&
-                nx.direction == DIR_OUT && nx.object > 0) {
-                vf.cval = (sid_t)nx.object;
-                vf.base = e->st->type_base;
-                vf.n = e->st->type_n;
-                vf.tbm = (e->gs && (size_t)vf.cval < e->gs->d_tbm.size())
-                             ? e->gs->d_tbm[vf.cval]
-                             : nullptr;
-                vf.type_of = e->d_type_of;
-                if (vf.tbm || vf.type_of) vf.on = 1;
-            }
-        }
-        {
-            TIME_BEGIN(e);
-            launch_expand(e, cur_tbl, out_tbl, G, vf);
-            TIME_END(e, CAT_EXPAND);
-        }
-        e->v2c[-(o + 1)] = e->ncols;
-        e->ncols = oc;
-        e->bound = e->cap_rows;  // fan-out unknown until a sync point
-        e->cur ^= 1;
-        e->tbl_view = nullptr;             // k_scan_mid committed for this chain
-        e->step += vf.on ? 2 : 1;  // fused verify consumed the filter
-        return WK_OK;
-    }
-    hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, e->stream, e->d_state,
-                       (uint64_t)e->cap_rows);
-    e->cur ^= 1;
-    e->tbl_view = nullptr;
-    e->step++;
-    return WK_OK;
+    const int ostat = e->var_stat(c.o);
+    if (!c.seg || c.seg->num_buckets == 0)
+        return step_absent_segment(e, c, ostat);
+    if (ostat != 0) return step_filter(e, c, ostat);
+    return step_k2u(e, c);
 }
 
 extern "C" int32_t wk_engine_execute_one_pattern(wk_engine_t *e, int64_t *nrows_out) {
@@ -3443,18 +1643,11 @@ extern "C" int32_t wk_engine_execute_filter_list(wk_engine_t *e,
     const sid_t *cur_tbl = cur_table(e);
     sid_t *out_tbl = (sid_t *)e->tbl[e->cur ^ 1].p;
     TIME_BEGIN(e);
-    fparams P{e->d_verts, (const sid_t *)e->misc.p, 0, 1, cur_tbl, e->ncols,
-              col, 0u, pat.direction, PK_NORMAL, PM_LIST, 0, 0u, 0, n,
-              e->d_type_of, 0, 0, 0, nullptr, nullptr, nullptr, 0, 0, 0};
-    hipLaunchKernelGGL(k_filter_tpr, dim3(grid_for(e->bound)), dim3(BLOCK), 0,
-                       e->stream, P, 0, /*commit*/ 0, 0,
-                       e->d_state, e->d_stats, out_tbl);
+    launch_filter_tpr(e, fparams_list(e, (const sid_t *)e->misc.p, cur_tbl,
+                                      col, pat.direction, 0, n), 0, out_tbl);
     TIME_END(e, CAT_FILTER);
-    hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, e->stream, e->d_state,
-                       (uint64_t)e->cap_rows);
-    e->cur ^= 1;
-    e->tbl_view = nullptr;
-    e->step++;
+    launch_commit(e);
+    finish_step(e, 0, e->ncols, e->bound, 1);
     int32_t rc = sync_state(e);
     if (rc == WK_OK && nrows_out) *nrows_out = e->nrows;
     return rc;

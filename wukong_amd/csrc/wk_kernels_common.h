@@ -1,0 +1,127 @@
+// wk_kernels_common.h — device-side state words, probe and membership helpers shared by every kernel family.
+// Included by gpu_engine.hip only (one translation unit).
+#pragma once
+
+// ---------------------------------------------------------------------
+// device kernels
+// ---------------------------------------------------------------------
+
+// probe modes
+enum { PK_NORMAL = 0, PK_INDEX = 1 };   // key = [vid|pid|dir] vs [0|val|dir]
+enum { PM_SIZE = 0,    // k2u: write edge count per row
+       PM_CONST = 1,   // k2c: flag = (const in edge list)
+       PM_COL = 2,     // k2k: flag = (row's other col in edge list)
+       PM_LIST = 3,    // c2k/i2k: flag = (row col value in a FIXED list)
+       PM_EQ = 4 };    // k2c via reversed functional map: flag = (col == cval)
+
+// device query state (see engine): [0]=nrows [1]=scan total [2]=overflow
+// flag [3]=required rows; stats[0..6] = algorithmic bytes per category
+enum { S_NROWS = 0, S_TOTAL = 1, S_ERR = 2, S_REQ = 3, S_OVF = 4,
+       S_DONE = 5, S_INROWS = 6, S_WORDS = 7 };
+enum { CAT_PROBE = 0, CAT_SCAN, CAT_EXPAND, CAT_FILTER, CAT_COPY, CAT_SPLIT,
+       CAT_OTHER, CAT_COUNT };
+
+constexpr int SCAN_T = 256;  // scan tile = block size of the fused kernels
+
+__device__ __forceinline__ void count_bytes(uint64_t *stats, int cat,
+                                            uint64_t bytes) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && stats)
+        atomicAdd((unsigned long long *)&stats[cat], (unsigned long long)bytes);
+}
+
+// sorted-membership test: edge lists are ascending (loader sort,
+// base_loader.hpp:367-377) so binary search replaces the reference's
+// linear scan (sparql.hpp:430-470) with identical keep-row semantics.
+__device__ __forceinline__ bool bsearch_u32(const sid_t *a, uint64_t n, sid_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        uint64_t mid = (lo + hi) >> 1;
+        sid_t v = a[mid];
+        if (v < x) lo = mid + 1;
+        else if (v > x) hi = mid;
+        else return true;
+    }
+    return false;
+}
+
+// per-type membership bitmap: 1 bit per vid of [base, base+n)
+__device__ __forceinline__ bool tbm_has(const uint64_t *__restrict__ tbm,
+                                        uint64_t base, uint64_t n, sid_t v) {
+    const uint64_t ix = (uint64_t)v - base;
+    return ix < n && ((tbm[ix >> 6] >> (ix & 63)) & 1);
+}
+
+// CSR side-index entry of key v ({off:40|len:24}, wk_types.h), 0 = absent
+__device__ __forceinline__ uint64_t csr_entry(const fnpage_t *__restrict__ pg,
+                                              const uint64_t *__restrict__ entries,
+                                              uint64_t base, uint64_t n,
+                                              sid_t v) {
+    const uint32_t rk = rank_lookup(pg, base, n, v);
+    return rk == RANK_MISS ? 0 : entries[rk];
+}
+
+// No-drop verify of `v rdf:type cval` inside the verify-fused expansions
+// (k_expand_in / k_expand_big): bitmap when present, else dense type_of.
+// The engine treats multi-type entities (type_of == 0xFFFF) in three
+// DELIBERATELY different ways — keep them apart:
+//   - here: a miss (-> S_DONE -> k_verify_commit -> S_ERR -> safe re-run)
+//   - filter_keep: falls through to the hash probe
+//   - k_fn_gather: probes [v|TYPE|OUT]
+__device__ __forceinline__ bool typeof_nodrop_ok(
+    const uint64_t *__restrict__ tbm, const uint16_t *__restrict__ type_of,
+    uint64_t base, uint64_t n, sid_t cval, sid_t v) {
+    if (tbm) return tbm_has(tbm, base, n, v);
+    const uint64_t tix = (uint64_t)v - base;
+    const uint16_t t = (tix < n) ? type_of[tix] : 0;
+    return t != 0xFFFF && (sid_t)t == cval;
+}
+
+// one cluster-hash lookup: walk the bucket chain, 7 slot compares per
+// 128-B bucket (gstore.hpp:341-361 semantics)
+__device__ __forceinline__ void probe_one(const vertex_t *__restrict__ verts,
+                                          uint64_t bucket_start,
+                                          uint64_t num_buckets, uint64_t key,
+                                          uint64_t &eoff, uint64_t &esz) {
+    uint64_t bucket = bucket_start + hash_u64(key) % num_buckets;
+    while (true) {
+        const vertex_t *b = &verts[bucket * ASSOC];
+        uint64_t k0 = b[0].key, k1 = b[1].key, k2 = b[2].key, k3 = b[3].key;
+        uint64_t k4 = b[4].key, k5 = b[5].key, k6 = b[6].key, k7 = b[7].key;
+        int hit = -1;
+        if (k0 == key) hit = 0;
+        else if (k1 == key) hit = 1;
+        else if (k2 == key) hit = 2;
+        else if (k3 == key) hit = 3;
+        else if (k4 == key) hit = 4;
+        else if (k5 == key) hit = 5;
+        else if (k6 == key) hit = 6;
+        if (hit >= 0) {
+            uint64_t pp = b[hit].ptr;
+            eoff = ptr_off(pp);
+            esz = ptr_size(pp);
+            return;
+        }
+        if (k7 == KEY_EMPTY) { eoff = 0; esz = 0; return; }
+        bucket = key_vid(k7);
+    }
+}
+
+// continue a probe from a chained bucket (absolute bucket id)
+__device__ __forceinline__ void probe_chain(const vertex_t *__restrict__ verts,
+                                            uint64_t bucket, uint64_t key,
+                                            uint64_t &eoff, uint64_t &esz) {
+    while (true) {
+        const vertex_t *b = &verts[bucket * ASSOC];
+        int hit = -1;
+#pragma unroll
+        for (int i = 0; i < ASSOC - 1; i++)
+            if (b[i].key == key && hit < 0) hit = i;
+        if (hit >= 0) {
+            eoff = ptr_off(b[hit].ptr);
+            esz = ptr_size(b[hit].ptr);
+            return;
+        }
+        if (b[ASSOC - 1].key == KEY_EMPTY) { eoff = 0; esz = 0; return; }
+        bucket = key_vid(b[ASSOC - 1].key);
+    }
+}

@@ -1,0 +1,692 @@
+// wk_kernels_expand.h — probe / scan / expand kernels and the 1-thread state kernels.
+// Included by gpu_engine.hip only (one translation unit).
+#pragma once
+
+// Fused known_to_unknown front half: contiguous-chunk thread-per-row
+// probe + in-kernel exclusive prefix of the edge counts (local prefix +
+// per-block sums; k_scan_mid finishes across blocks).  64 rows in
+// flight per wave between scan barriers — MLP for DRAM-random probes
+// (gstore.hpp:341-361; replaces gpu_hash.cu:94-324 + the thrust scan).
+__global__ void k_probe_scan(const vertex_t *__restrict__ verts,
+                             const sid_t *__restrict__ tbl, int ncols,
+                             int col, uint32_t pid, int dir, int key_mode,
+                             uint64_t bucket_start, uint64_t num_buckets,
+                             uint64_t *__restrict__ d_state,
+                             uint64_t *__restrict__ d_stats,
+                             uint64_t *__restrict__ d_eoff,
+                             uint32_t *__restrict__ d_cnt,
+                             uint64_t *__restrict__ d_pre,
+                             uint64_t *__restrict__ bsums)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 + 128 + 8 + 12));
+    const int64_t chunk = (nrows + gridDim.x - 1) / gridDim.x;
+    const int64_t start = (int64_t)blockIdx.x * chunk;
+    const int64_t end = min(start + chunk, nrows);
+    __shared__ uint64_t sh[SCAN_T];
+    uint64_t carry = 0;
+
+    // 2-deep pipeline: the NEXT tile row's first bucket is issued before
+    // this tile's scan phase, so its ~900-cycle HBM latency hides under
+    // the LDS scan + barriers (loads to registers stay in flight across
+    // s_barrier; hipcc waits at first use)
+    auto key_of = [&](int64_t r) {
+        sid_t v = tbl[r * ncols + col];
+        return (key_mode == PK_NORMAL) ? key_pack(v, pid, (uint64_t)dir)
+                                       : key_pack(0, v, (uint64_t)dir);
+    };
+    uint64_t nkey = 0, nbucket = 0;
+    uint64_t pk[ASSOC];
+    uint64_t pp[ASSOC - 1];
+    bool have_pref = false;
+    if (start + threadIdx.x < end) {
+        nkey = key_of(start + threadIdx.x);
+        nbucket = bucket_start + hash_u64(nkey) % num_buckets;
+        const vertex_t *b = &verts[nbucket * ASSOC];
+#pragma unroll
+        for (int i = 0; i < ASSOC; i++) pk[i] = b[i].key;
+#pragma unroll
+        for (int i = 0; i < ASSOC - 1; i++) pp[i] = b[i].ptr;
+        have_pref = true;
+    }
+    for (int64_t base = start; base < end; base += SCAN_T) {
+        const int64_t r = base + threadIdx.x;
+        uint64_t eoff = 0, esz = 0;
+        uint64_t key = nkey;
+        uint64_t ck[ASSOC], cp[ASSOC - 1];
+        bool have = have_pref;
+        if (have) {
+#pragma unroll
+            for (int i = 0; i < ASSOC; i++) ck[i] = pk[i];
+#pragma unroll
+            for (int i = 0; i < ASSOC - 1; i++) cp[i] = pp[i];
+        }
+        // issue next tile's first bucket
+        const int64_t rn = base + SCAN_T + threadIdx.x;
+        have_pref = false;
+        if (rn < end) {
+            nkey = key_of(rn);
+            nbucket = bucket_start + hash_u64(nkey) % num_buckets;
+            const vertex_t *b = &verts[nbucket * ASSOC];
+#pragma unroll
+            for (int i = 0; i < ASSOC; i++) pk[i] = b[i].key;
+#pragma unroll
+            for (int i = 0; i < ASSOC - 1; i++) pp[i] = b[i].ptr;
+            have_pref = true;
+        }
+        if (have) {
+            // resolve the prefetched bucket; rare chains fall back to the walk
+            int hit = -1;
+#pragma unroll
+            for (int i = 0; i < ASSOC - 1; i++)
+                if (ck[i] == key && hit < 0) hit = i;
+            if (hit >= 0) {
+                eoff = ptr_off(cp[hit]);
+                esz = ptr_size(cp[hit]);
+            } else if (ck[ASSOC - 1] != KEY_EMPTY) {
+                // rare (~13% of buckets): continue down the chain
+                probe_chain(verts, key_vid(ck[ASSOC - 1]), key, eoff, esz);
+            }
+            d_eoff[r] = eoff;
+            d_cnt[r] = (uint32_t)esz;
+        }
+        sh[threadIdx.x] = esz;
+        __syncthreads();
+        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
+            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += x;
+            __syncthreads();
+        }
+        if (r < end) d_pre[r] = carry + sh[threadIdx.x] - esz;
+        carry += sh[SCAN_T - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) bsums[blockIdx.x] = (start < end) ? carry : 0;
+}
+
+// CSR-indexed known_to_unknown front half (non-functional segments):
+// the 128-B cluster-hash bucket walk becomes a 16-B page + 8-B entry
+// lookup ({edge_off:40|len:24}, rank-compressed like the fn maps).
+// Two phases, following the two-phase fn lesson: a barrier-free 1:1
+// gather writes (eoff, cnt); k_scan_local then runs the chunked
+// prefix exactly as k_probe_scan produced it, so the expansion
+// kernels consume the identical layout.
+__global__ void k_csr_gather(const sid_t *__restrict__ tbl, int ncols,
+                             int col,
+                             const fnpage_t *__restrict__ pg,
+                             const uint64_t *__restrict__ entries,
+                             uint64_t base, uint64_t n,
+                             const uint64_t *__restrict__ d_state,
+                             uint64_t *__restrict__ d_stats,
+                             uint64_t *__restrict__ d_eoff,
+                             uint32_t *__restrict__ d_cnt)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 + 16 + 8 + 12));
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t e =
+            csr_entry(pg, entries, base, n, tbl[r * ncols + col]);
+        d_eoff[r] = csr_off(e);
+        d_cnt[r] = csr_len(e);
+    }
+}
+
+// Counting variant for the EXACT fused `k2u + ?v rdf:type CONST`
+// compaction (nothing optimistic: output == expansion+filter output):
+// per row, CSR entry lookup, then ONE walk of the edge list counting
+// values whose type-bitmap bit is set.  d_cnt gets the FILTERED count
+// (the scan then yields exact output positions); d_eoff packs
+// {edge_off:40 | full_len:24} so the writer can re-walk the list.
+__global__ void k_csr_gather_tf(const sid_t *__restrict__ tbl, int ncols,
+                                int col,
+                                const fnpage_t *__restrict__ pg,
+                                const uint64_t *__restrict__ entries,
+                                uint64_t base, uint64_t n,
+                                const sid_t *__restrict__ edges,
+                                const uint64_t *__restrict__ tbm,
+                                uint64_t t_base, uint64_t t_n,
+                                const uint64_t *__restrict__ d_state,
+                                uint64_t *__restrict__ d_stats,
+                                uint64_t *__restrict__ d_eoff,
+                                uint32_t *__restrict__ d_cnt)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 + 16 + 8 + 12));
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t e =
+            csr_entry(pg, entries, base, n, tbl[r * ncols + col]);
+        const uint64_t off = csr_off(e);
+        const uint32_t len = csr_len(e);
+        uint32_t keep = 0;
+        for (uint32_t k = 0; k < len; k++)
+            keep += tbm_has(tbm, t_base, t_n, edges[off + k]) ? 1u : 0u;
+        d_eoff[r] = e;  // {off:40|len:24} for the writer's re-walk
+        d_cnt[r] = keep;
+    }
+}
+
+// writer for the fused compaction: re-walk the edge list, emit only
+// passing values at the exact scanned positions (wave-ballot ranks for
+// the big-row pass below)
+template <int NC>
+__global__ void k_expand_tf(const sid_t *__restrict__ tbl, int ncols,
+                            const sid_t *__restrict__ edges,
+                            const uint64_t *__restrict__ d_eoff,
+                            const uint32_t *__restrict__ d_cnt,
+                            const uint64_t *__restrict__ d_pre,
+                            const uint64_t *__restrict__ bsums, int G,
+                            const uint64_t *__restrict__ tbm,
+                            uint64_t t_base, uint64_t t_n,
+                            uint64_t *__restrict__ d_state, uint64_t cap,
+                            uint64_t *__restrict__ d_stats,
+                            uint32_t *__restrict__ ovf,
+                            sid_t *__restrict__ out)
+{
+    const int64_t nrows = (int64_t)d_state[S_INROWS];
+    const int64_t chunk = (nrows + G - 1) / G;
+    constexpr int oc = NC + 1;
+    (void)ncols;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t keep = d_cnt[r];
+        if (!keep) continue;
+        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        if (basep >= cap) continue;
+        const uint64_t e = d_eoff[r];
+        const uint64_t off = csr_off(e);
+        const uint32_t len = csr_len(e);
+        if (len > 32) {
+            unsigned long long i = atomicAdd(
+                (unsigned long long *)&d_state[S_OVF], 1ull);
+            ovf[i] = (uint32_t)r;
+            continue;
+        }
+        sid_t row[NC];
+#pragma unroll
+        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
+        sid_t *dst = out + (int64_t)basep * oc;
+        uint32_t w = 0;
+        for (uint32_t k = 0; k < len && w < keep; k++) {
+            sid_t v = edges[off + k];
+            if (!tbm_has(tbm, t_base, t_n, v)) continue;
+            if (basep + w >= cap) break;
+#pragma unroll
+            for (int c = 0; c < NC; c++) dst[c] = row[c];
+            dst[NC] = v;
+            dst += oc;
+            w++;
+        }
+    }
+}
+
+template <int NC>
+__global__ void k_expand_tf_big(const sid_t *__restrict__ tbl, int ncols,
+                                const sid_t *__restrict__ edges,
+                                const uint64_t *__restrict__ d_eoff,
+                                const uint32_t *__restrict__ d_cnt,
+                                const uint64_t *__restrict__ d_pre,
+                                const uint64_t *__restrict__ bsums, int G,
+                                const uint64_t *__restrict__ tbm,
+                                uint64_t t_base, uint64_t t_n,
+                                uint64_t *__restrict__ d_state, uint64_t cap,
+                                const uint32_t *__restrict__ ovf,
+                                sid_t *__restrict__ out)
+{
+    const int64_t nq = (int64_t)d_state[S_OVF];
+    const int64_t nrows = (int64_t)d_state[S_INROWS];
+    const int64_t chunk = (nrows + G - 1) / G;
+    constexpr int oc = NC + 1;
+    (void)ncols;
+    const int lane = threadIdx.x & 63;
+    const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t q = w0; q < nq; q += nw) {
+        const int64_t r = ovf[q];
+        const uint64_t e = d_eoff[r];
+        const uint64_t off = csr_off(e);
+        const uint32_t len = csr_len(e);
+        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        if (basep >= cap) continue;
+        sid_t row[NC];
+#pragma unroll
+        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
+        uint64_t wbase = 0;  // passing-rank base across 64-edge chunks
+        for (uint32_t k0 = 0; k0 < len; k0 += 64) {
+            const uint32_t k = k0 + lane;
+            bool pass = false;
+            sid_t v = 0;
+            if (k < len) {
+                v = edges[off + k];
+                pass = tbm_has(tbm, t_base, t_n, v);
+            }
+            uint64_t mask = __ballot(pass);
+            if (pass) {
+                uint64_t pos = basep + wbase +
+                               (uint64_t)__popcll(mask & ((1ull << lane) - 1));
+                if (pos < cap) {
+                    sid_t *dst = out + (int64_t)pos * oc;
+#pragma unroll
+                    for (int c = 0; c < NC; c++) dst[c] = row[c];
+                    dst[NC] = v;
+                }
+            }
+            wbase += (uint64_t)__popcll(mask);
+        }
+    }
+}
+
+// chunked exclusive prefix of d_cnt -> d_pre + per-chunk sums (same
+// chunk math as k_probe_scan so the expansion kernels are unchanged)
+__global__ void k_scan_local(const uint32_t *__restrict__ d_cnt,
+                             const uint64_t *__restrict__ d_state,
+                             uint64_t *__restrict__ d_pre,
+                             uint64_t *__restrict__ bsums)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    const int G = gridDim.x;
+    const int64_t chunk = (nrows + G - 1) / G;
+    const int64_t start = (int64_t)blockIdx.x * chunk;
+    const int64_t end = min(start + chunk, (int64_t)nrows);
+    __shared__ uint64_t sh[SCAN_T];
+    uint64_t carry = 0;
+    for (int64_t base = start; base < end; base += SCAN_T) {
+        const int64_t r = base + threadIdx.x;
+        uint64_t esz = (r < end) ? d_cnt[r] : 0;
+        sh[threadIdx.x] = esz;
+        __syncthreads();
+        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
+            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += x;
+            __syncthreads();
+        }
+        if (r < end) d_pre[r] = carry + sh[threadIdx.x] - esz;
+        carry += sh[SCAN_T - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) bsums[blockIdx.x] = (start < end) ? carry : 0;
+}
+
+// fn-expansion scatter (phase 4 of gather -> scan_local -> scan_mid ->
+// scatter): deterministic positions, no atomics, barrier-free.
+template <int NC>
+__global__ void k_fn_scatter(const sid_t *__restrict__ tbl,
+                             const sid_t *__restrict__ d_val,
+                             const uint32_t *__restrict__ d_cnt,
+                             const uint64_t *__restrict__ d_pre,
+                             const uint64_t *__restrict__ bsums, int G,
+                             const uint64_t *__restrict__ d_state,
+                             uint64_t *__restrict__ d_stats,
+                             sid_t *__restrict__ out)
+{
+    const int64_t nrows = (int64_t)d_state[S_INROWS];  // scan_mid committed
+    constexpr int oc = NC + 1;
+    count_bytes(d_stats, CAT_EXPAND, (uint64_t)nrows * (4 + 4 * NC + 4 * oc));
+    const int64_t chunk = (nrows + G - 1) / G;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        if (!d_cnt[r]) continue;
+        uint64_t pos = d_pre[r] + bsums[r / chunk];
+        sid_t *dst = out + (int64_t)pos * oc;
+        const sid_t *srow = tbl + r * NC;
+#pragma unroll
+        for (int c = 0; c < NC; c++) dst[c] = srow[c];
+        dst[NC] = d_val[r];
+    }
+}
+
+// finish the scan across blocks: exclusive over the G block sums
+// (single block).  Fuses the step commit (k_commit semantics): the
+// pipeline total is known here, the following scatter kernels read
+// the INPUT row count from the S_INROWS snapshot, and S_OVF (the
+// big-row queue this chain is about to fill) starts clean — saving
+// the separate 1-thread commit launch per k2u/fn step.
+__global__ void k_scan_mid(uint64_t *__restrict__ bsums, int G,
+                           uint64_t cap, uint64_t *__restrict__ d_state)
+{
+    __shared__ uint64_t sh[SCAN_T];
+    uint64_t carry = 0;
+    for (int base = 0; base < G; base += SCAN_T) {
+        int i = base + threadIdx.x;
+        uint64_t x = (i < G) ? bsums[i] : 0;
+        sh[threadIdx.x] = x;
+        __syncthreads();
+        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
+            uint64_t v = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += v;
+            __syncthreads();
+        }
+        if (i < G) bsums[i] = carry + sh[threadIdx.x] - x;
+        carry += sh[SCAN_T - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        d_state[S_INROWS] = d_state[S_NROWS];
+        uint64_t t = carry;
+        if (t > cap) {
+            d_state[S_ERR] = 1;
+            d_state[S_REQ] = max(d_state[S_REQ], t);
+            t = cap;
+        }
+        d_state[S_NROWS] = t;
+        d_state[S_TOTAL] = 0;
+        d_state[S_OVF] = 0;
+    }
+}
+
+// advance: nrows = min(total, cap); flag overflow for the host re-run
+// (replaces the reference's rbuf-overflow assert, gpu_engine_cuda.hpp:185).
+// Stays a 1-thread kernel: a commit fused into the last finishing block
+// of a wide producer bumps one done-word per block, which serializes at
+// ~88 atomics/us and costs more than this launch (k_peer_step, a single
+// block, commits inline).
+__global__ void k_commit(uint64_t *__restrict__ d_state, uint64_t cap) {
+    uint64_t t = d_state[S_TOTAL];
+    if (t > cap) {
+        d_state[S_ERR] = 1;
+        d_state[S_REQ] = max(d_state[S_REQ], t);
+        t = cap;
+    }
+    d_state[S_NROWS] = t;
+    // reset the accumulators for the next step (saves a 3us k_zero_words
+    // launch per step — the state kernels were 12% of suite GPU time)
+    d_state[S_TOTAL] = 0;
+    d_state[S_OVF] = 0;
+}
+
+__global__ void k_set_state(uint64_t *__restrict__ d_state, uint64_t nrows) {
+    d_state[S_NROWS] = nrows;
+    d_state[S_TOTAL] = 0;
+    d_state[S_OVF] = 0;
+}
+
+// device projection to required-var columns (sparql.hpp:1510-1536)
+struct cols8 { int32_t c[8]; };
+__global__ void k_project(const sid_t *__restrict__ tbl, int ncols,
+                          const uint64_t *__restrict__ d_state, cols8 cols,
+                          int rc, sid_t *__restrict__ out)
+{
+    const int64_t n = (int64_t)d_state[S_NROWS];
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * rc;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        int64_t i = t / rc;
+        int j = (int)(t - i * rc);
+        int c = cols.c[j];
+        out[t] = (c >= 0) ? tbl[i * ncols + c] : (sid_t)0xFFFFFFFFu;
+    }
+}
+
+__global__ void k_publish_state(const uint64_t *__restrict__ d_state,
+                                const uint64_t *__restrict__ d_stats,
+                                uint64_t *__restrict__ h_pin) {
+    for (int i = 0; i < S_WORDS; i++) h_pin[i] = d_state[i];
+    for (int i = 0; i < CAT_COUNT; i++) h_pin[8 + i] = d_stats[i];
+    // sticky error flag (h_pin slot 7): survives across back-to-back
+    // graph replays whose own begin kernels clear d_state — the
+    // one-sync-per-pass path checks and clears it host-side
+    if (d_state[S_ERR]) h_pin[7] = 1;
+}
+
+// Input-centric expansion (known_to_unknown back half,
+// sparql.hpp:325-367): thread r writes its deg outputs at
+// pre[r]+bsums[chunk(r)] — no per-output binary search (the
+// output-centric version paid 2-3 DRAM lines of prefix walk per output
+// row).  Rows with deg > 32 go to an overflow queue handled by
+// k_expand_big with one WAVE per row (lanes stride the edge list).
+// verify-fused expansion (captured graphs only): when the NEXT pattern
+// is a no-drop `?v rdf:type CONST` filter on the NEW column (warm-pass
+// hint), each written value is checked inline (bitmap or dense type_of;
+// misses count into S_DONE -> k_verify_commit -> S_ERR -> safe re-run)
+// and the separate full-table verify pass disappears.
+template <int NC>
+__global__ void k_expand_in(const sid_t *__restrict__ tbl, int ncols,
+                            const sid_t *__restrict__ edges,
+                            const uint64_t *__restrict__ d_eoff,
+                            const uint32_t *__restrict__ d_cnt,
+                            const uint64_t *__restrict__ d_pre,
+                            const uint64_t *__restrict__ bsums, int G,
+                            uint64_t *__restrict__ d_state, uint64_t cap,
+                            uint64_t *__restrict__ d_stats,
+                            uint32_t *__restrict__ ovf,
+                            const uint64_t *__restrict__ vtbm,
+                            const uint16_t *__restrict__ v_type_of,
+                            uint64_t v_type_base, uint64_t v_type_n,
+                            sid_t v_cval, int verify,
+                            sid_t *__restrict__ out)
+{
+    // k_scan_mid already committed: S_INROWS = the input row count,
+    // S_NROWS = the (capped) output total
+    const int64_t nrows = (int64_t)d_state[S_INROWS];
+    const int64_t chunk = (nrows + G - 1) / G;
+    constexpr int oc = NC + 1;
+    (void)ncols;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t deg = d_cnt[r];
+        if (!deg) continue;
+        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        if (basep >= cap) continue;  // overflow: flagged by k_commit
+        if (deg > 32) {
+            unsigned long long i = atomicAdd(
+                (unsigned long long *)&d_state[S_OVF], 1ull);
+            ovf[i] = (uint32_t)r;
+            continue;
+        }
+        if (basep + deg > cap) deg = (uint32_t)(cap - basep);
+        sid_t row[NC];
+#pragma unroll
+        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
+        const sid_t *el = edges + d_eoff[r];
+        sid_t *dst = out + (int64_t)basep * oc;
+        uint32_t miss = 0;
+        for (uint32_t k = 0; k < deg; k++) {
+#pragma unroll
+            for (int c = 0; c < NC; c++) dst[c] = row[c];
+            sid_t v = el[k];
+            dst[NC] = v;
+            dst += oc;
+            if (verify)
+                miss += typeof_nodrop_ok(vtbm, v_type_of, v_type_base,
+                                         v_type_n, v_cval, v) ? 0u : 1u;
+        }
+        if (miss)
+            atomicAdd((unsigned long long *)&d_state[S_DONE],
+                      (unsigned long long)miss);
+    }
+    // algorithmic bytes for the whole expansion (counted once; includes
+    // the big-row pass): total*(edge 4 + write 4*oc) + nrows*(row 4*ncols
+    // + cnt/pre/eoff 20)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        atomicAdd((unsigned long long *)&d_stats[CAT_EXPAND],
+                  (unsigned long long)(d_state[S_NROWS] * (4 + 4 * oc) +
+                                       (uint64_t)nrows * (4 * ncols + 20)));
+}
+
+// big-fanout rows: one wave per queued row, lanes stride the edge list
+// (coalesced writes: adjacent lanes write adjacent output rows)
+template <int NC>
+__global__ void k_expand_big(const sid_t *__restrict__ tbl, int ncols,
+                             const sid_t *__restrict__ edges,
+                             const uint64_t *__restrict__ d_eoff,
+                             const uint32_t *__restrict__ d_cnt,
+                             const uint64_t *__restrict__ d_pre,
+                             const uint64_t *__restrict__ bsums, int G,
+                             uint64_t *__restrict__ d_state, uint64_t cap,
+                             const uint32_t *__restrict__ ovf,
+                             const uint64_t *__restrict__ vtbm,
+                             const uint16_t *__restrict__ v_type_of,
+                             uint64_t v_type_base, uint64_t v_type_n,
+                             sid_t v_cval, int verify,
+                             sid_t *__restrict__ out)
+{
+    const int64_t nq = (int64_t)d_state[S_OVF];
+    const int64_t nrows = (int64_t)d_state[S_INROWS];
+    const int64_t chunk = (nrows + G - 1) / G;
+    constexpr int oc = NC + 1;
+    (void)ncols;
+    const int lane = threadIdx.x & 63;
+    const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t q = w0; q < nq; q += nw) {
+        const int64_t r = ovf[q];
+        uint64_t deg = d_cnt[r];
+        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        if (basep >= cap) continue;
+        if (basep + deg > cap) deg = cap - basep;
+        sid_t row[NC];
+#pragma unroll
+        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
+        const sid_t *el = edges + d_eoff[r];
+        uint32_t miss = 0;
+        for (uint64_t k = lane; k < deg; k += 64) {
+            sid_t *dst = out + (int64_t)(basep + k) * oc;
+#pragma unroll
+            for (int c = 0; c < NC; c++) dst[c] = row[c];
+            sid_t v = el[k];
+            dst[NC] = v;
+            if (verify)
+                miss += typeof_nodrop_ok(vtbm, v_type_of, v_type_base,
+                                         v_type_n, v_cval, v) ? 0u : 1u;
+        }
+        if (miss)
+            atomicAdd((unsigned long long *)&d_state[S_DONE],
+                      (unsigned long long)miss);
+    }
+}
+
+// known_to_unknown over a FUNCTIONAL predicate (every key deg==1,
+// rank-compressed map): the probe+scan+expand pipeline collapses into
+// a page+value gather pair + compacted append, with an optional fused
+// `?v rdf:type CONST` filter on the NEW column (plan pairs like Q1's
+// ugDegreeFrom -> University).  Two phases: a 1:1 grid-stride GATHER
+// (the measured-fast k_expand_fn_map shape — no barriers between the
+// dependent page/value loads) writes each row's resolved object (0 =
+// miss/filtered) to a scratch stream; the COMPACT phase then reads it
+// SEQUENTIALLY with the block-aggregated scan.  The round-1 single-pass
+// form interleaved the gathers with 16 scan barriers per tile and ran
+// 4-5x slower than its own gather cost (169 vs 36 us on Q1's 6.4M-row
+// step).  Multi-type (0xFFFF) falls back to a probe of [val|TYPE|OUT].
+// Output rows <= input rows, so capacity can never overflow.
+__global__ void k_fn_gather(const sid_t *__restrict__ tbl, int ncols,
+                            const fnpage_t *__restrict__ fn_pg,
+                            const sid_t *__restrict__ fn_vals,
+                            uint64_t fn_base, uint64_t fn_n, int col,
+                            int use_typeof, sid_t fcval,
+                            const uint16_t *__restrict__ type_of,
+                            const uint64_t *__restrict__ tbm,
+                            uint64_t type_base, uint64_t type_n,
+                            const vertex_t *__restrict__ verts,
+                            const sid_t *__restrict__ edges,
+                            uint64_t f_bstart, uint64_t f_nbuckets,
+                            const uint64_t *__restrict__ d_state,
+                            uint64_t *__restrict__ d_stats,
+                            sid_t *__restrict__ d_val,
+                            uint32_t *__restrict__ d_cnt)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_EXPAND,
+                (uint64_t)nrows * (24 + 4 + (use_typeof ? 2 : 0)));
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        sid_t v = tbl[r * ncols + col];
+        sid_t tv = fn_lookup(fn_pg, fn_vals, fn_base, fn_n, v);
+        if (tv && use_typeof) {
+            if (tbm) {  // bitmap: decision is exact (multi-type incl.)
+                if (!tbm_has(tbm, type_base, type_n, tv)) tv = 0;
+            } else {
+                uint64_t tix = (uint64_t)tv - type_base;
+                uint16_t t = (tix < type_n) ? type_of[tix] : 0;
+                if (t != 0xFFFF) {
+                    if ((sid_t)t != fcval) tv = 0;
+                } else {
+                    uint64_t eo = 0, es = 0;
+                    probe_one(verts, f_bstart, f_nbuckets,
+                              key_pack(tv, TYPE_ID, (uint64_t)DIR_OUT), eo,
+                              es);
+                    if (!(es && bsearch_u32(edges + eo, es, fcval))) tv = 0;
+                }
+            }
+        }
+        d_val[r] = tv;
+        d_cnt[r] = tv ? 1u : 0u;
+    }
+}
+
+// OPTIMISTIC functional k2u: used ONLY inside captured graphs for
+// steps whose warm pass dropped no rows (store is immutable, so the
+// observation holds for replays; a miss at runtime still flips S_ERR
+// via k_commit_map and the caller falls back to the safe path).  The
+// 1:1 write needs no scan/compaction and coalesces perfectly.
+template <int NC>
+__global__ void k_expand_fn_map(const sid_t *__restrict__ tbl,
+                                const fnpage_t *__restrict__ fn_pg,
+                                const sid_t *__restrict__ fn_vals,
+                                uint64_t fn_base, uint64_t fn_n, int col,
+                                int use_typeof,
+                                const uint64_t *__restrict__ tbm,
+                                const uint16_t *__restrict__ type_of,
+                                uint64_t type_base, uint64_t type_n,
+                                sid_t fcval,
+                                uint64_t *__restrict__ d_state,
+                                uint64_t *__restrict__ d_stats,
+                                sid_t *__restrict__ out)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    constexpr int oc = NC + 1;
+    count_bytes(d_stats, CAT_EXPAND,
+                (uint64_t)nrows * (24 + (use_typeof ? 1 : 0) + oc * 4));
+    uint32_t miss = 0;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        sid_t v = tbl[r * NC + col];
+        sid_t tv = fn_lookup(fn_pg, fn_vals, fn_base, fn_n, v);
+        bool ok = tv != 0;
+        if (ok && use_typeof) {
+            if (tbm) {
+                ok = tbm_has(tbm, type_base, type_n, tv);
+            } else {
+                uint64_t tix = (uint64_t)tv - type_base;
+                uint16_t t = (tix < type_n) ? type_of[tix] : 0;
+                ok = ((sid_t)t == fcval);  // 0xFFFF never matches ->
+                                           // counts as miss -> fallback
+            }
+        }
+        miss += ok ? 0u : 1u;
+        sid_t *dst = out + r * oc;
+#pragma unroll
+        for (int c = 0; c < NC; c++) dst[c] = tbl[r * NC + c];
+        dst[NC] = tv;
+    }
+    if (miss)
+        atomicAdd((unsigned long long *)&d_state[S_OVF],
+                  (unsigned long long)miss);
+}
+
+// verify-fused expansion epilogue: any inline-typeof miss (S_DONE)
+// flips S_ERR so the replay is discarded and the safe path re-runs
+__global__ void k_verify_commit(uint64_t *__restrict__ d_state) {
+    if (d_state[S_DONE]) {
+        d_state[S_ERR] = 1;
+        d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
+        d_state[S_DONE] = 0;
+    }
+}
+
+// commit for the optimistic map: row count unchanged; any miss flags
+// S_ERR so the replay result is discarded and the safe path re-runs
+__global__ void k_commit_map(uint64_t *__restrict__ d_state) {
+    if (d_state[S_OVF]) {
+        d_state[S_ERR] = 1;
+        d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
+    }
+    d_state[S_TOTAL] = 0;
+    d_state[S_OVF] = 0;
+}
+
+__global__ void k_zero_words(uint64_t *p, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
+}

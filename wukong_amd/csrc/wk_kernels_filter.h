@@ -1,0 +1,354 @@
+// wk_kernels_filter.h — filter, VERSATILE and OPTIONAL kernels.
+// Included by gpu_engine.hip only (one translation unit).
+#pragma once
+
+// Filter predicate (k2c/k2k/c2k/i2k keep-row decision of the one-pass
+// filter k_filter_tpr below).
+struct fparams {
+    const vertex_t *verts;
+    const sid_t *edges;
+    uint64_t bucket_start, num_buckets;
+    const sid_t *tbl;
+    int ncols, col;
+    uint32_t pid;
+    int dir, key_mode, probe_mode, col2;
+    sid_t cval;
+    uint64_t list_off, list_sz;
+    const uint16_t *type_of;
+    uint64_t type_base, type_n;
+    int use_typeof;
+    const uint64_t *tbm;
+    const fnpage_t *fn_pg;
+    const sid_t *fn_vals;
+    uint64_t fn_base, fn_n;
+    int fn_swap;
+};
+
+__device__ __forceinline__ bool filter_keep(const fparams &P, int64_t r) {
+    sid_t v = P.tbl[r * P.ncols + P.col];
+    if (P.use_typeof) {
+        if (P.tbm)
+            // per-type bitmap: 1 bit/vid, whole map LLC-resident —
+            // exact (multi-type included), no probe fallback
+            return tbm_has(P.tbm, P.type_base, P.type_n, v);
+        uint64_t idx = (uint64_t)v - P.type_base;
+        uint16_t t = (idx < P.type_n) ? P.type_of[idx] : 0;
+        if (t != 0xFFFF) return (sid_t)t == P.cval;
+    }
+    if (P.probe_mode == PM_EQ) {
+        // reversed functional map resolved host-side: the edge exists
+        // iff the row value IS the precomputed vertex
+        return v == P.cval;
+    }
+    if (P.probe_mode == PM_LIST && !P.use_typeof)
+        return bsearch_u32(P.edges + P.list_off, P.list_sz, v);
+    if (P.fn_pg) {
+        // functional predicate: the row's single object replaces the
+        // probe + edge-list search (rank-compressed map: 16-B page +
+        // 4-B value vs 148 bytes of hash traffic).  fn_swap: the
+        // REVERSED direction is functional — check fn[other col] == col.
+        sid_t a = v, b;
+        if (P.probe_mode == PM_CONST) b = P.cval;
+        else b = P.tbl[r * P.ncols + P.col2];
+        if (P.fn_swap) { sid_t t_ = a; a = b; b = t_; }
+        sid_t tv = fn_lookup(P.fn_pg, P.fn_vals, P.fn_base, P.fn_n, a);
+        return tv && tv == b;
+    }
+    uint64_t key = (P.key_mode == PK_NORMAL)
+                       ? key_pack(v, P.pid, (uint64_t)P.dir)
+                       : key_pack(0, v, (uint64_t)P.dir);
+    uint64_t eoff = 0, esz = 0;
+    probe_one(P.verts, P.bucket_start, P.num_buckets, key, eoff, esz);
+    sid_t tgt = (P.probe_mode == PM_CONST) ? P.cval
+                                           : P.tbl[r * P.ncols + P.col2];
+    return esz && bsearch_u32(P.edges + eoff, esz, tgt);
+}
+
+__device__ __forceinline__ uint64_t filter_bytes_per_row(const fparams &P) {
+    return (P.use_typeof ? 6
+            : P.fn_pg ? 24
+            : P.probe_mode == PM_LIST ? 12
+                                      : (4 + 128 + 8 + 64)) +
+           8 * P.ncols;
+}
+
+// One-pass filter: keep + wavefront-ballot compaction.  Each tile
+// costs ONE global cursor atomic per block — a single word saturates
+// at ~88 atomics/us (microarch row `dequeue`), so ~2048 in-flight
+// blocks serialize ~23 us per tile ROUND; fine up to ~1-2M rows.
+// (A flags+scan+scatter pipeline was tried for larger tables and
+// measured SLOWER at suite keep-rates — extra passes cost more than
+// the atomics they save.)  Row order is engine-internal; parity is
+// set-level (sparql.hpp:455-476 semantics).
+__global__ void k_filter_tpr(fparams P, int verify_only,
+                             uint64_t *__restrict__ d_state,
+                             uint64_t *__restrict__ d_stats,
+                             sid_t *__restrict__ out_tbl)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * filter_bytes_per_row(P));
+    constexpr int K = 4;
+    __shared__ unsigned long long s_base;
+    __shared__ unsigned int s_cnt;
+    __shared__ unsigned int s_wbase[SCAN_T / 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const int ncols = P.ncols;
+    const sid_t *__restrict__ tbl = P.tbl;
+    const int64_t tile = (int64_t)blockDim.x * K;
+    const int64_t stride = (int64_t)gridDim.x * tile;
+
+    for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows; base += stride) {
+        bool keep[K];
+        int64_t rr[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const int64_t r = base + k * SCAN_T + threadIdx.x;
+            rr[k] = r;
+            keep[k] = r < nrows && filter_keep(P, r);
+        }
+        if (verify_only) {
+            // identity-verified filter (captured graphs): the warm pass
+            // saw zero drops; every replay still checks every row and
+            // flags S_ERR on any miss (no writes, no table flip)
+            uint32_t miss = 0;
+#pragma unroll
+            for (int k = 0; k < K; k++)
+                miss += (rr[k] < nrows && !keep[k]) ? 1u : 0u;
+            if (miss)
+                atomicAdd((unsigned long long *)&d_state[S_OVF],
+                          (unsigned long long)miss);
+            continue;
+        }
+        if (threadIdx.x == 0) s_cnt = 0;
+        __syncthreads();
+        uint64_t mask[K];
+        uint32_t wtot = 0;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            mask[k] = __ballot(keep[k]);
+            wtot += (uint32_t)__popcll(mask[k]);
+        }
+        if (lane == 0) s_wbase[wid] = atomicAdd(&s_cnt, wtot);
+        __syncthreads();
+        if (threadIdx.x == 0)
+            s_base = s_cnt ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
+                                       (unsigned long long)s_cnt)
+                           : 0;
+        __syncthreads();
+        uint32_t wpos = s_wbase[wid];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            if (keep[k]) {
+                uint64_t pos = s_base + wpos +
+                               (uint32_t)__popcll(mask[k] &
+                                                  ((1ull << lane) - 1));
+                sid_t *dst = out_tbl + (int64_t)pos * ncols;
+                const sid_t *srow = tbl + rr[k] * ncols;
+                for (int c = 0; c < ncols; c++) dst[c] = srow[c];
+            }
+            wpos += (uint32_t)__popcll(mask[k]);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------
+// VERSATILE predicate-variable ops (sparql.hpp:556-744): one kernel
+// covers known/const_unknown_unknown (append p [, y] columns) and
+// known/const_unknown_const (keep one row per matching p).  Block per
+// input row; the row vid's predicate list comes from the dense vp CSR;
+// each predicate probes its own (pid,dir) segment via the device
+// segment table.  Appends use the global S_TOTAL cursor (k_commit
+// finalises; overflow -> S_ERR/S_REQ re-run like every other op).
+// ---------------------------------------------------------------------
+enum { VU_END_NEW = 0, VU_END_CONST = 1 };
+__global__ void k_vu(const vertex_t *__restrict__ verts,
+                     const sid_t *__restrict__ edges,
+                     const sid_t *__restrict__ in_tbl, int ncols, int col,
+                     sid_t const_start,
+                     const uint32_t *__restrict__ vp_off,
+                     const sid_t *__restrict__ vp_edges,
+                     uint64_t vp_base, uint64_t vp_n,
+                     const seg_t *__restrict__ segtab, uint32_t max_pid,
+                     int dir, int end_mode, sid_t cval,
+                     sid_t *__restrict__ out, int out_cols, uint64_t cap_rows,
+                     uint64_t *__restrict__ d_state,
+                     uint64_t *__restrict__ d_stats)
+{
+    const uint64_t nrows = (col >= 0) ? d_state[S_NROWS] : 1;
+    uint64_t bytes = 0;
+    for (uint64_t r = blockIdx.x; r < nrows; r += gridDim.x) {
+        sid_t vid = (col >= 0) ? in_tbl[r * ncols + col] : const_start;
+        uint64_t idx = (uint64_t)vid - vp_base;
+        if (idx >= vp_n) continue;
+        uint64_t plo = vp_off[idx], phi = vp_off[idx + 1];
+        bytes += 8;
+        for (uint64_t pi = plo + threadIdx.x; pi < phi; pi += blockDim.x) {
+            sid_t p = vp_edges[pi];
+            uint64_t eoff = 0, esz = 0;
+            if (p <= max_pid) {
+                const seg_t sg = segtab[p * 2 + dir];
+                if (sg.num_buckets)
+                    probe_one(verts, sg.bucket_start, sg.num_buckets,
+                              key_pack((uint64_t)vid, (uint64_t)p,
+                                       (uint64_t)dir),
+                              eoff, esz);
+            }
+            bytes += 4 + 148;
+            if (end_mode == VU_END_CONST) {
+                if (esz && bsearch_u32(edges + eoff, esz, cval)) {
+                    uint64_t pos = atomicAdd(
+                        (unsigned long long *)&d_state[S_TOTAL], 1ull);
+                    if (pos < cap_rows) {
+                        sid_t *dst = out + pos * out_cols;
+                        for (int c = 0; c < ncols; c++)
+                            dst[c] = in_tbl[r * ncols + c];
+                        dst[ncols] = p;
+                        bytes += (uint64_t)out_cols * 4;
+                    }
+                }
+            } else {
+                uint64_t pos = atomicAdd(
+                    (unsigned long long *)&d_state[S_TOTAL],
+                    (unsigned long long)esz);
+                for (uint64_t k = 0; k < esz && pos + k < cap_rows; k++) {
+                    sid_t *dst = out + (pos + k) * out_cols;
+                    for (int c = 0; c < ncols; c++)
+                        dst[c] = in_tbl[r * ncols + c];
+                    dst[ncols] = p;
+                    dst[ncols + 1] = edges[eoff + k];
+                }
+                bytes += esz * ((uint64_t)out_cols * 4 + 4);
+            }
+        }
+    }
+    if (bytes)
+        atomicAdd((unsigned long long *)&d_stats[CAT_EXPAND],
+                  (unsigned long long)bytes);
+}
+
+// ---------------------------------------------------------------------
+// OPTIONAL-mode operators (sparql.hpp:100-170, 316-375; BGP-only like
+// the reference, query.hpp:722-733): rows are never dropped — a row
+// whose pattern fails keeps BLANK_ID in every column first bound inside
+// the OPTIONAL group (blank_mask) and clears its matched flag.  This is
+// a correctness/coverage path (no LUBM/WatDiv benchmark uses OPTIONAL),
+// so the expansion uses a plain global append cursor.
+// ---------------------------------------------------------------------
+__global__ void k_filter_opt(const vertex_t *__restrict__ verts,
+                             const sid_t *__restrict__ edges,
+                             uint64_t bucket_start, uint64_t num_buckets,
+                             sid_t *__restrict__ tbl, int ncols, int col,
+                             uint32_t pid, int dir, int probe_mode, int col2,
+                             sid_t cval, uint64_t list_off, uint64_t list_sz,
+                             uint32_t blank_mask, uint8_t *__restrict__ flags,
+                             uint64_t *__restrict__ d_state,
+                             uint64_t *__restrict__ d_stats)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * (4 + 128 + 8 + 64));
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        sid_t v = tbl[r * ncols + col];
+        bool ok;
+        if (probe_mode == PM_LIST) {
+            ok = bsearch_u32(edges + list_off, list_sz, v);
+        } else {
+            uint64_t eoff = 0, esz = 0;
+            if (v != BLANK_ID && num_buckets)
+                probe_one(verts, bucket_start, num_buckets,
+                          key_pack((uint64_t)v, (uint64_t)pid, (uint64_t)dir),
+                          eoff, esz);
+            sid_t tgt = (probe_mode == PM_CONST) ? cval
+                                                 : tbl[r * ncols + col2];
+            ok = esz && tgt != BLANK_ID && bsearch_u32(edges + eoff, esz, tgt);
+        }
+        if (!ok) {
+            if (flags[r]) {
+                for (int c = 0; c < ncols; c++)
+                    if ((blank_mask >> c) & 1)
+                        tbl[r * ncols + c] = BLANK_ID;
+            }
+            flags[r] = 0;
+        }
+    }
+}
+
+__global__ void k_expand_opt(const vertex_t *__restrict__ verts,
+                             const sid_t *__restrict__ edges,
+                             const sid_t *__restrict__ tbl, int ncols,
+                             int col, uint32_t pid, int dir, int key_mode,
+                             uint64_t bucket_start, uint64_t num_buckets,
+                             const uint8_t *__restrict__ flags_in,
+                             uint8_t *__restrict__ flags_out,
+                             sid_t *__restrict__ out, uint64_t cap,
+                             uint64_t *__restrict__ d_state,
+                             uint64_t *__restrict__ d_stats)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    const int oc = ncols + 1;
+    count_bytes(d_stats, CAT_EXPAND, (uint64_t)nrows * (4 + 128 + 8));
+    // block-aggregated append (one global atomic per 256-row tile)
+    // replaces the round-1 per-row cursors — a single cursor word
+    // saturates at ~88 atomics/us (microarch row `dequeue`)
+    __shared__ unsigned long long s_base;
+    __shared__ uint64_t sh[SCAN_T];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < nrows;
+         base += stride) {
+        const int64_t r = base + threadIdx.x;
+        uint64_t eoff = 0, esz = 0, emit = 0;
+        uint8_t m = 0;
+        sid_t v = 0;
+        if (r < nrows) {
+            v = tbl[r * ncols + col];
+            m = flags_in[r];
+            if (m && v != BLANK_ID && num_buckets) {
+                uint64_t key = (key_mode == PK_NORMAL)
+                                   ? key_pack((uint64_t)v, (uint64_t)pid,
+                                              (uint64_t)dir)
+                                   : key_pack(0, (uint64_t)v, (uint64_t)dir);
+                probe_one(verts, bucket_start, num_buckets, key, eoff, esz);
+            }
+            // unmatched / blank / no edges: keep the row, BLANK new
+            // col; the matched flag survives unchanged
+            // (sparql.hpp:328-334, 352-356)
+            emit = (!m || v == BLANK_ID || esz == 0) ? 1 : esz;
+        }
+        sh[threadIdx.x] = emit;
+        __syncthreads();
+        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
+            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
+            __syncthreads();
+            sh[threadIdx.x] += x;
+            __syncthreads();
+        }
+        const uint64_t my_end = sh[threadIdx.x];
+        const uint64_t block_total = sh[SCAN_T - 1];
+        if (threadIdx.x == SCAN_T - 1)
+            s_base = block_total
+                         ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
+                                     (unsigned long long)block_total)
+                         : 0;
+        __syncthreads();
+        if (r < nrows) {
+            uint64_t pos = s_base + my_end - emit;
+            if (!m || v == BLANK_ID || esz == 0) {
+                if (pos < cap) {
+                    sid_t *dst = out + pos * oc;
+                    for (int c = 0; c < ncols; c++) dst[c] = tbl[r * ncols + c];
+                    dst[ncols] = BLANK_ID;
+                    flags_out[pos] = m;
+                }
+            } else {
+                for (uint64_t k = 0; k < esz && pos + k < cap; k++) {
+                    sid_t *dst = out + (pos + k) * oc;
+                    for (int c = 0; c < ncols; c++) dst[c] = tbl[r * ncols + c];
+                    dst[ncols] = edges[eoff + k];
+                    flags_out[pos + k] = 1;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}

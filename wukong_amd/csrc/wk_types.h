@@ -71,19 +71,32 @@ struct alignas(16) fnpage_t {
     uint32_t pad;
 };
 
+// Page lookup shared by the fn maps and the CSR side index: the rank of
+// key v in the packed array, or RANK_MISS (a real rank counts keys of a
+// u32 vid span, so it never reaches 2^32-1).
+constexpr uint32_t RANK_MISS = 0xFFFFFFFFu;
+WK_HD uint32_t rank_lookup(const fnpage_t *pages, uint64_t base, uint64_t n,
+                           sid_t v) {
+    uint64_t idx = (uint64_t)v - base;
+    if (idx >= n) return RANK_MISS;
+    const fnpage_t p = pages[idx >> 6];
+    if (!((p.bits >> (idx & 63)) & 1)) return RANK_MISS;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return p.rank + (uint32_t)__popcll(p.bits & ((1ull << (idx & 63)) - 1));
+#else
+    return p.rank + (uint32_t)__builtin_popcountll(p.bits & ((1ull << (idx & 63)) - 1));
+#endif
+}
+
 WK_HD sid_t fn_lookup(const fnpage_t *pages, const sid_t *vals,
                       uint64_t base, uint64_t n, sid_t v) {
-    uint64_t idx = (uint64_t)v - base;
-    if (idx >= n) return 0;
-    const fnpage_t p = pages[idx >> 6];
-    if (!((p.bits >> (idx & 63)) & 1)) return 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t r = p.rank + (uint32_t)__popcll(p.bits & ((1ull << (idx & 63)) - 1));
-#else
-    uint32_t r = p.rank + (uint32_t)__builtin_popcountll(p.bits & ((1ull << (idx & 63)) - 1));
-#endif
-    return vals[r];
+    uint32_t r = rank_lookup(pages, base, n, v);
+    return r == RANK_MISS ? 0 : vals[r];
 }
+
+// CSR side-index entry {edge_off:40 | len:24}; 0 = key absent
+WK_HD uint64_t csr_off(uint64_t e) { return e >> 24; }
+WK_HD uint32_t csr_len(uint64_t e) { return (uint32_t)(e & 0xFFFFFF); }
 
 // 128-bit slot (vertex.hpp:154-157)
 struct vertex_t { uint64_t key; uint64_t ptr; };
