@@ -10,6 +10,7 @@ import pytest
 import wukong_amd as wk
 from wukong_amd import Plan, queries as Q
 from tests.oracle_util import OracleCtx, sort_rows
+from tests.synth_graph import env
 
 pytestmark = pytest.mark.gpu
 
@@ -35,11 +36,7 @@ def test_side_index_fallback_parity(lubm4, oracle4):
     (fn maps, CSR, type bitmaps — WK_FN=0 WK_CSR=0 WK_TBM=0) must give
     identical bindings.  Covers the probe/expand/filter base kernels
     that the side-indexed default store routes around."""
-    old = {}
-    for k in ("WK_FN", "WK_CSR", "WK_TBM"):
-        old[k] = os.environ.get(k)
-        os.environ[k] = "0"
-    try:
+    with env(WK_FN=0, WK_CSR=0, WK_TBM=0):
         store = wk.Store(lubm4)
         eng = wk.Engine(store, device=0)
         for name, plan in Q.ALL.items():
@@ -47,12 +44,6 @@ def test_side_index_fallback_parity(lubm4, oracle4):
             want = sort_rows(oracle4.run_query(plan))
             assert got.shape == want.shape, (name, got.shape, want.shape)
             assert np.array_equal(got, want), name
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def test_wide_chain_all_column_counts():
@@ -92,18 +83,8 @@ def test_wide_chain_all_column_counts():
         for _ in range(2):
             assert eng.graph_run(gid) == w.shape[0], ("graph", p.nvars)
 
-    old = {}
-    for k in ("WK_FN", "WK_CSR", "WK_TBM"):
-        old[k] = os.environ.get(k)
-        os.environ[k] = "0"
-    try:
+    with env(WK_FN=0, WK_CSR=0, WK_TBM=0):
         check_rows(wk.Engine(wk.Store(triples), device=0), "no side index")
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def test_golden_fixture_gpu(eng4, store4):

@@ -1556,6 +1556,9 @@ extern "C" int32_t wk_engine_execute_one_pattern(wk_engine_t *e, int64_t *nrows_
     const int in_cur = e->cur;
     const int in_ncols = e->ncols;
     const int in_step = e->step;  // a fused step consumes TWO patterns
+    // a zero-copy i2u/c2u input lives in the (immutable) store, not in
+    // tbl[in_cur]: the step drops the view, the re-run must see it again
+    const sid_t *const in_view = e->tbl_view;
     const std::vector<int32_t> in_v2c = e->v2c;
     int32_t rc = exec_pattern(e);
     if (rc == WK_OK && nrows_out) {
@@ -1566,6 +1569,7 @@ extern "C" int32_t wk_engine_execute_one_pattern(wk_engine_t *e, int64_t *nrows_
             // now current again); re-run this pattern
             int64_t need = (int64_t)e->h_pin[S_REQ];
             e->cur = in_cur;
+            e->tbl_view = in_view;
             e->nrows = in_rows;
             e->ncols = in_ncols;
             e->v2c = in_v2c;
