@@ -38,8 +38,14 @@
  *   k_fn_gather/k_fn_scatter — functional-predicate rank-compressed
  *                       map k2u (deg==1 segments; page+value gathers);
  *                       k_expand_fn_map = optimistic 1:1 inside graphs
- *   k_commit, k_commit_map, k_verify_commit, k_set_state, k_zero_words,
- *   k_publish_state, k_project — 1-thread state kernels, projection
+ *   k_commit, k_set_state, k_begin_state, k_zero_words,
+ *   k_publish_state, k_project — 1-thread state kernels, projection.
+ *                       A query's begin zeroing rides on its first state
+ *                       write (k_begin_state); the optimistic kernels
+ *                       count guard misses into the sticky S_DONE word,
+ *                       which k_publish_state alone turns into S_ERR —
+ *                       no per-step commit for steps that keep the row
+ *                       count
  *  wk_kernels_filter.h
  *   k_filter_tpr      — fused probe/typeof filter + block compaction
  *                       (replaces gpu_hash.cu:326-445,523-585);
@@ -64,7 +70,10 @@
  *                       (read-only view, no copy kernel)
  *   hipGraph replay   — wk_engine_graph_build/run/launch: a fixed plan
  *                       replays as ONE launch, with warm-pass-derived
- *                       no-drop specialization verified on every replay
+ *                       no-drop specialization verified on every replay;
+ *                       patterns the warm pass saw run on an empty
+ *                       table are host bookkeeping only (empty-tail
+ *                       truncation, guarded by the publish)
  */
 #include "wk_store.h"
 #include "../../include/wukong_abi.h"
@@ -211,6 +220,10 @@ struct wk_engine {
     int64_t bound = 0;   // host-side upper bound on rows (grid sizing)
 
     bool light = false;  // single-kernel fast path ran (h_pin self-published)
+    // begin_query's d_state zeroing, deferred so the query's first state
+    // write (k_begin_state) performs it; any other first launch flushes
+    // it with k_zero_words (flush_begin)
+    bool zero_pending = false;
     bool hinting = false;  // graph-build hint pass: per-PATTERN row counts
                            // needed, so multi-step fusions are disabled
     int remote_step_idx = -1;  // pattern to run via the xGMI peer path
@@ -247,12 +260,16 @@ struct wk_engine {
         int ncols = 0, cur = 0, nvars = 0;
         int64_t bound = 0;
         bool light = false;
+        const sid_t *view = nullptr;  // final table is a zero-copy view
     };
     std::vector<wk_graph> graphs;
     int capturing = 0;
     // per-pattern-step no-drop hints from the graph build's warm pass
     // (consulted ONLY while capturing)
     std::vector<uint8_t> capture_hint;
+    // last pattern to execute while capturing: the warm pass saw the
+    // table empty from there to the end of the plan (-1 = run them all)
+    int capture_empty_after = -1;
 
     // timing (WK_KERNEL_TIMING=1)
     bool timing = false;
@@ -689,10 +706,35 @@ extern "C" int32_t wk_engine_begin_query(wk_engine_t *e, const wk_plan_t *plan) 
     e->light = false;
     int32_t rc = grow_caps(e, e->cap_rows, plan->nvars);
     if (rc) return rc;
-    // reset nrows + overflow flags on device (async, cheap kernel)
+    // reset nrows + overflow flags on device: deferred to the query's
+    // first launch (k_begin_state in step_start / load_common, else
+    // flush_begin)
+    e->zero_pending = true;
+    return WK_OK;
+}
+
+// Perform a still-pending begin_query zeroing on its own: called ahead
+// of every launch that reads or publishes d_state and is not itself a
+// begin-aware state write (launch_set_rows).
+static void flush_begin(wk_engine *e) {
+    if (!e->zero_pending) return;
+    e->zero_pending = false;
     hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, e->stream, e->d_state,
                        S_WORDS);
-    return WK_OK;
+}
+
+// Set the row count of a fresh table.  As the first launch of a query it
+// also does begin_query's zeroing (one kernel); later it keeps
+// k_set_state's meaning and leaves S_ERR/S_REQ/S_DONE alone.
+static void launch_set_rows(wk_engine *e, uint64_t nrows) {
+    if (e->zero_pending) {
+        e->zero_pending = false;
+        hipLaunchKernelGGL(k_begin_state, dim3(1), dim3(1), 0, e->stream,
+                           e->d_state, nrows);
+    } else {
+        hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream,
+                           e->d_state, nrows);
+    }
 }
 
 // begin without the device-state zeroing kernel (the light fast path's
@@ -709,6 +751,7 @@ static int32_t begin_light(wk_engine *e, const wk_plan_t *plan) {
     e->tbl_view = nullptr;
     e->bound = 0;
     e->light = true;
+    e->zero_pending = false;  // k_light2 writes S_NROWS/S_ERR itself
     return grow_caps(e, e->cap_rows, plan->nvars);
 }
 
@@ -721,8 +764,7 @@ static int32_t load_common(wk_engine *e, int64_t nrows, int32_t ncols,
     e->ncols = ncols;
     if (v2c_map) e->v2c.assign(v2c_map, v2c_map + e->nvars);
     e->step = pattern_step;
-    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream, e->d_state,
-                       (uint64_t)nrows);
+    launch_set_rows(e, (uint64_t)nrows);
     return WK_OK;
 }
 
@@ -753,16 +795,25 @@ extern "C" int32_t wk_engine_load_rbuf_device(wk_engine_t *e, const sid_t *dev_t
 }
 
 // publish device state to pinned memory + sync; refresh host nrows/stats
+static void launch_publish(wk_engine *e, int expect_empty) {
+    flush_begin(e);
+    hipLaunchKernelGGL(k_publish_state, dim3(1), dim3(1), 0, e->stream,
+                       e->d_state, e->d_stats, e->h_pin, expect_empty);
+}
+
 static int32_t sync_state(wk_engine *e) {
-    if (!e->light)
-        hipLaunchKernelGGL(k_publish_state, dim3(1), dim3(1), 0, e->stream,
-                           e->d_state, e->d_stats, e->h_pin);
+    if (!e->light) launch_publish(e, 0);
     HIP_CHECK(stream_sync(e->stream));
     resolve_timing(e);
     e->nrows = (int64_t)e->h_pin[S_NROWS];
     e->bound = e->nrows;
     for (int i = 0; i < CAT_COUNT; i++) e->cat_bytes[i] = (double)e->h_pin[8 + i];
-    if (e->h_pin[S_ERR]) return WK_ERR_CAP;
+    if (e->h_pin[S_ERR]) {
+        // reported here: the sticky slot belongs to the pipelined
+        // graph_launch window and must not fail a later wk_engine_sync
+        e->h_pin[7] = 0;
+        return WK_ERR_CAP;
+    }
     return WK_OK;
 }
 
@@ -775,8 +826,7 @@ static int32_t sync_state_grow(wk_engine *e) {
     e->nrows = 0;  // nothing worth preserving across the re-run
     int32_t rc2 = grow_caps(e, need + need / 4, e->cap_cols);
     if (rc2) return rc2;
-    hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, e->stream,
-                       e->d_state, S_WORDS);
+    e->zero_pending = true;  // the next launch clears the flags
     return WK_ERR_CAP;
 }
 
@@ -853,10 +903,6 @@ static void finish_step(wk_engine *e, ssid_t new_var, int out_cols,
 static void launch_commit(wk_engine *e) {
     hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, e->stream, e->d_state,
                        (uint64_t)e->cap_rows);
-}
-static void launch_commit_map(wk_engine *e) {
-    hipLaunchKernelGGL(k_commit_map, dim3(1), dim3(1), 0, e->stream,
-                       e->d_state);
 }
 
 // fparams of a fixed-list membership filter (c2k/i2k): keep the rows
@@ -937,9 +983,8 @@ static void launch_expand_t(wk_engine *e, const sid_t *cur_tbl, sid_t *out_tbl,
                        (uint64_t)e->cap_rows,
                        (uint32_t *)e->ovf.p, vf.tbm, vf.type_of, vf.base,
                        vf.n, vf.cval, vf.on, out_tbl);
-    if (vf.on)
-        hipLaunchKernelGGL(k_verify_commit, dim3(1), dim3(1), 0, e->stream,
-                           e->d_state);
+    // a fused verify's misses sit in the sticky S_DONE word until the
+    // publish: no epilogue launch
 }
 
 template <int NC>
@@ -1229,8 +1274,7 @@ static int32_t step_start(wk_engine *e, const step_ctx &c, bool index_start) {
     uint64_t off = ptr ? (uint64_t)(ptr - st->edges.data()) : 0;
     int32_t rc = grow_caps(e, (int64_t)sz, e->nvars);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream, e->d_state,
-                       sz);
+    launch_set_rows(e, sz);
     // the new table REPLACES whatever was current: ?o is column 0
     e->v2c[-(c.o + 1)] = 0;
     finish_step(e, 0, 1, (int64_t)sz, 1);
@@ -1282,8 +1326,9 @@ static int32_t step_filter(wk_engine *e, const step_ctx &c, int ostat) {
     // identity-verified filter: the graph build's warm pass saw this
     // step keep every row, so the captured graph runs a read-only
     // verification (typeof/membership checks on every row, misses ->
-    // S_ERR -> replay discarded + safe fallback) with no compaction
-    // write and no table flip (q7's COURSE filter: 86us -> ~40us)
+    // sticky S_DONE -> S_ERR at the publish -> replay discarded + safe
+    // fallback) with no compaction write, no table flip and no commit
+    // launch (q7's COURSE filter: 86us -> ~40us)
     const bool verify_only = hint_nodrop(e, e->step);
     TIME_BEGIN(e);
     int use_typeof = (pmode == PM_CONST && (sid_t)p == TYPE_ID &&
@@ -1331,8 +1376,8 @@ static int32_t step_filter(wk_engine *e, const step_ctx &c, int ostat) {
     launch_filter_tpr(e, P, verify_only ? 1 : 0, c.out_tbl);
     TIME_END(e, CAT_FILTER);
     if (verify_only) {
-        // no rows written: the table stays where it is
-        launch_commit_map(e);
+        // no rows written, S_NROWS/S_TOTAL untouched: the table stays
+        // where it is
         finish_step_in_place(e, 0, e->ncols, e->bound, 1);
         return WK_OK;
     }
@@ -1369,8 +1414,8 @@ static int32_t step_k2u_fn(wk_engine *e, const step_ctx &c,
         launch_expand_fn(e, c.cur_tbl, c.out_tbl, d_pg, d_vals, c.col,
                          fuse, fcval, fseg);
     TIME_END(e, CAT_EXPAND);
-    // the scan pipeline committed in k_scan_mid; the 1:1 map did not
-    if (opt) launch_commit_map(e);
+    // the scan pipeline committed in k_scan_mid; the 1:1 map keeps the
+    // row count and needs no commit
     finish_step(e, c.o, e->ncols + 1, e->bound, fuse ? 2 : 1);
     return WK_OK;
 }
@@ -1501,9 +1546,19 @@ static int32_t step_k2u(wk_engine *e, const step_ctx &c) {
 // counts live on device; a non-NULL nrows_out forces a sync (step API).
 static int32_t exec_pattern(wk_engine *e) {
     if (!e || e->step >= (int)e->pats.size()) return WK_ERR_STATE;
-    if (e->step == e->remote_step_idx) return exec_pattern_remote(e);
     const wk_store *st = e->st;
     const wk_pattern_t pat = e->pats[e->step];
+    // a start step's state write doubles as the query's begin kernel
+    // (launch_set_rows); every other operator reads d_state, so a
+    // pending begin zeroing goes first
+    const bool index_start =
+        (e->step == 0 && pat.subject >= 0 && is_tpid(pat.subject));
+    const bool start =
+        e->step != e->remote_step_idx && !e->opt_mode && pat.predicate >= 0 &&
+        (index_start || (pat.subject >= 0 && pat.object < 0 &&
+                         e->var2col(pat.object) < 0));
+    if (!start) flush_begin(e);
+    if (e->step == e->remote_step_idx) return exec_pattern_remote(e);
     // OPT-group kernels write the current table IN PLACE (BLANK fill):
     // a zero-copy i2u view must be materialised first
     if (e->opt_mode && e->tbl_view) {
@@ -1515,9 +1570,7 @@ static int32_t exec_pattern(wk_engine *e) {
     if (e->opt_mode) return step_optional(e, c);
     if (c.p < 0) return step_versatile(e, c);
 
-    const bool index_start = (e->step == 0 && c.s >= 0 && is_tpid(c.s));
-    if (index_start || (c.s >= 0 && c.o < 0 && e->var2col(c.o) < 0))
-        return step_start(e, c, index_start);
+    if (start) return step_start(e, c, index_start);
     if (c.s >= 0) return step_const_to_known(e, c);
 
     // ---- known start ----
@@ -1577,10 +1630,8 @@ extern "C" int32_t wk_engine_execute_one_pattern(wk_engine_t *e, int64_t *nrows_
             e->bound = in_rows;
             int32_t rc2 = grow_caps(e, need + need / 4, e->cap_cols);
             if (rc2) return rc2;
-            hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, e->stream,
-                               e->d_state, S_WORDS);
-            hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream,
-                               e->d_state, (uint64_t)in_rows);
+            e->zero_pending = true;  // clear the flags with the row reset
+            launch_set_rows(e, (uint64_t)in_rows);
             rc = exec_pattern(e);
             if (rc) return rc;
         }
@@ -1796,6 +1847,7 @@ extern "C" int32_t wk_engine_fetch_result(wk_engine_t *e, const wk_plan_t *plan,
         for (int j = 0; j < plan->nrequired; j++)
             cols.c[j] = e->var2col(plan->required_vars[j]);
         sid_t *out_tbl = (sid_t *)e->tbl[e->cur ^ 1].p;
+        flush_begin(e);
         TIME_BEGIN(e);
         hipLaunchKernelGGL(k_project, dim3(grid_for(e->cap_rows)), dim3(BLOCK), 0,
                            e->stream, cur_table(e), e->ncols,
@@ -1859,6 +1911,38 @@ extern "C" int32_t wk_engine_fetch_raw(wk_engine_t *e, wk_result_t *out) {
     return WK_OK;
 }
 
+// ---- empty-tail truncation of captured plans -------------------------
+// Host bookkeeping of one pattern that runs on an EMPTY table: bind the
+// variable a full run would bind, launch nothing.  false = a shape whose
+// effect is not "append at most one column to the same table" (a
+// const/index start REPLACES the table, a predicate variable appends
+// two columns, an unbound subject is an invalid plan): such a tail is
+// executed, not skipped.
+static bool skip_empty_pattern(const wk_pattern_t &pat,
+                               std::vector<int32_t> &v2c, int &ncols) {
+    auto col = [&](ssid_t v) { return v < 0 ? v2c[-(v + 1)] : -1; };
+    if (pat.predicate < 0) return false;
+    if (pat.subject >= 0)  // const_to_known keeps the layout
+        return pat.object < 0 && col(pat.object) >= 0;
+    if (col(pat.subject) < 0) return false;
+    if (pat.object < 0 && col(pat.object) < 0) v2c[-(pat.object + 1)] = ncols++;
+    return true;
+}
+
+// The rest of the plan on an empty table: the engine's host state ends
+// up exactly where a full run leaves it (v2c, ncols, step; bound 0).
+// The in-capture publish guards the assumption (expect_empty).
+static int32_t skip_empty_tail(wk_engine *e) {
+    while (e->step < (int)e->pats.size()) {
+        if (!skip_empty_pattern(e->pats[e->step], e->v2c, e->ncols))
+            return WK_ERR_PLAN;  // graph_warm_hints validated the tail
+        e->step++;
+    }
+    e->bound = 0;
+    e->nrows = 0;
+    return WK_OK;
+}
+
 // asynchronous whole-plan submission: enqueue the full launch chain and
 // return without any sync (pipelined multi-engine execution — the
 // reference proxy's in-flight window, proxy.hpp:477-525)
@@ -1905,10 +1989,88 @@ extern "C" int32_t wk_engine_submit(wk_engine_t *e, const wk_plan_t *plan) {
         return WK_OK;
     }
     while (e->step < (int)e->pats.size()) {
+        // captured plan with an empty tail: nothing is launched for the
+        // patterns the warm pass saw run on zero rows
+        if (e->capturing && e->capture_empty_after >= 0 &&
+            e->step > e->capture_empty_after)
+            return skip_empty_tail(e);
         rc = exec_pattern(e);
         if (rc) return rc;
     }
     return WK_OK;
+}
+
+// WK_FORCE_EMPTY_HINT=<k> (test-only, read at graph build): assume the
+// table is empty after pattern k whatever the warm pass saw, so the
+// expect_empty guard's failing branch can be exercised
+static int force_empty_hint() {
+    const char *v = getenv("WK_FORCE_EMPTY_HINT");
+    return v ? atoi(v) : -1;
+}
+
+// Warm + hint passes shared by both graph builders.  The warm pass
+// settles scratch capacities so the capture never allocates.  The
+// step-wise pass then records (a) which pattern steps dropped no rows
+// and (b) the last pattern after which the table is empty through the
+// end of the plan (*empty_after, -1 = none or nothing to skip).  The
+// store is immutable, so both observations hold for every replay; the
+// replay still guards them (sticky S_DONE misses, expect_empty) and
+// raises S_ERR when one fails.
+static int32_t graph_warm_hints(wk_engine *e, const wk_plan_t *plan,
+                                std::vector<uint8_t> &hint,
+                                int *empty_after) {
+    *empty_after = -1;
+    for (int attempt = 0; attempt < 4; attempt++) {
+        int32_t rc = wk_engine_submit(e, plan);
+        if (rc) return rc;
+        rc = sync_state_grow(e);
+        if (rc == WK_OK) break;
+        if (rc != WK_ERR_CAP) return rc;
+    }
+    const int np = std::max(plan->npatterns, 0);
+    hint.assign((size_t)np, 0);
+    int32_t rc = wk_engine_begin_query(e, plan);
+    if (rc) return rc;
+    // host layout after each step, keyed by the last pattern it consumed
+    // (the skipped tail's bookkeeping starts from one of these)
+    struct layout { int last; std::vector<int32_t> v2c; int ncols; };
+    std::vector<layout> seen;
+    e->hinting = true;  // per-pattern counts: no multi-step fusions
+    int64_t prev = -1;
+    int empty_at = -1;
+    while (e->step < (int)e->pats.size()) {
+        const int at = e->step;
+        int64_t n = 0;
+        rc = wk_engine_execute_one_pattern(e, &n);
+        if (rc) { e->hinting = false; return rc; }
+        if (n == prev && at < np) hint[at] = 1;
+        prev = n;
+        seen.push_back({e->step - 1, e->v2c, e->ncols});
+        if (n != 0) empty_at = -1;
+        else if (empty_at < 0) empty_at = e->step - 1;
+    }
+    e->hinting = false;
+    const int forced = force_empty_hint();
+    if (forced >= 0) empty_at = forced;
+    if (empty_at < 0 || empty_at >= np - 1) return WK_OK;  // nothing to skip
+    for (const layout &l : seen) {
+        if (l.last < empty_at) continue;
+        // the tail must be pure bookkeeping (skip_empty_pattern)
+        std::vector<int32_t> v2c = l.v2c;
+        int ncols = l.ncols;
+        for (int i = l.last + 1; i < np; i++)
+            if (!skip_empty_pattern(plan->patterns[i], v2c, ncols))
+                return WK_OK;
+        if (l.last < np - 1) *empty_after = l.last;
+        break;
+    }
+    return WK_OK;
+}
+
+static void end_capture_state(wk_engine *e) {
+    e->capturing = 0;
+    e->capture_hint.clear();
+    e->capture_empty_after = -1;
 }
 
 // ---------------------------------------------------------------------
@@ -1929,49 +2091,23 @@ extern "C" int32_t wk_engine_graph_build(wk_engine_t *e,
     // plans whose count the caller would misread
     if (plan->distinct || plan->limit >= 0 || plan->offset > 0)
         return WK_ERR_PLAN;
-    // warm pass: settle scratch capacities so capture never allocates
-    for (int attempt = 0; attempt < 4; attempt++) {
-        int32_t rc = wk_engine_submit(e, plan);
-        if (rc) return rc;
-        rc = sync_state_grow(e);
-        if (rc == WK_OK) break;
-        if (rc != WK_ERR_CAP) return rc;
-    }
-    // step-wise pass: record which pattern steps dropped no rows (the
-    // store is immutable, so these hints hold for every replay; the
-    // optimistic kernels still guard at runtime via S_ERR)
-    e->capture_hint.assign(std::max(plan->npatterns, 0), 0);
     {
-        int32_t rc = wk_engine_begin_query(e, plan);
+        int32_t rc = graph_warm_hints(e, plan, e->capture_hint,
+                                      &e->capture_empty_after);
         if (rc) return rc;
-        e->hinting = true;  // per-pattern counts: no multi-step fusions
-        int64_t prev = -1;
-        while (e->step < (int)e->pats.size()) {
-            const int at = e->step;
-            int64_t n = 0;
-            rc = wk_engine_execute_one_pattern(e, &n);
-            if (rc) { e->hinting = false; return rc; }
-            if (n == prev && at < (int)e->capture_hint.size())
-                e->capture_hint[at] = 1;
-            prev = n;
-        }
-        e->hinting = false;
     }
     e->capturing = 1;
     hipGraph_t g = nullptr;
     if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) !=
         hipSuccess) {
-        e->capturing = 0;
-        e->capture_hint.clear();
+        end_capture_state(e);
         return WK_ERR_HIP;
     }
     int32_t rc = wk_engine_submit(e, plan);
     if (rc == WK_OK && !e->light)
-        hipLaunchKernelGGL(k_publish_state, dim3(1), dim3(1), 0, e->stream,
-                           e->d_state, e->d_stats, e->h_pin);
+        launch_publish(e, e->capture_empty_after >= 0);
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
-    e->capturing = 0;
-    e->capture_hint.clear();
+    end_capture_state(e);
     if (rc != WK_OK || ce != hipSuccess || !g) {
         if (g) (void)hipGraphDestroy(g);
         // the capture aborted mid-chain: resynchronise engine state
@@ -1992,6 +2128,7 @@ extern "C" int32_t wk_engine_graph_build(wk_engine_t *e,
     wg.nvars = e->nvars;
     wg.bound = e->bound;
     wg.light = e->light;
+    wg.view = e->tbl_view;
     e->graphs.push_back(std::move(wg));
     *gid = (int32_t)e->graphs.size() - 1;
     return WK_OK;
@@ -2010,53 +2147,32 @@ extern "C" int32_t wk_engine_graph_build_suite(wk_engine_t *e,
                                                int32_t *gid) {
     if (!e || !plans || nplans <= 0 || !gid) return WK_ERR_STATE;
     std::vector<std::vector<uint8_t>> hints((size_t)nplans);
+    std::vector<int> empty_after((size_t)nplans, -1);
     for (int i = 0; i < nplans; i++) {
         const wk_plan_t *plan = &plans[i];
         if (plan->nopt > 0 || plan->nunion > 0 || plan->distinct ||
             plan->limit >= 0 || plan->offset > 0)
             return WK_ERR_PLAN;
-        // warm passes settle scratch capacities so capture never allocates
-        for (int attempt = 0; attempt < 4; attempt++) {
-            int32_t rc = wk_engine_submit(e, plan);
-            if (rc) return rc;
-            rc = sync_state_grow(e);
-            if (rc == WK_OK) break;
-            if (rc != WK_ERR_CAP) return rc;
-        }
-        hints[i].assign((size_t)std::max(plan->npatterns, 0), 0);
-        int32_t rc = wk_engine_begin_query(e, plan);
+        int32_t rc = graph_warm_hints(e, plan, hints[i], &empty_after[i]);
         if (rc) return rc;
-        e->hinting = true;  // per-pattern counts: no multi-step fusions
-        int64_t prev = -1;
-        while (e->step < (int)e->pats.size()) {
-            const int at = e->step;
-            int64_t n = 0;
-            rc = wk_engine_execute_one_pattern(e, &n);
-            if (rc) { e->hinting = false; return rc; }
-            if (n == prev && at < (int)hints[i].size()) hints[i][at] = 1;
-            prev = n;
-        }
-        e->hinting = false;
     }
     e->capturing = 1;
     hipGraph_t g = nullptr;
     if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) !=
         hipSuccess) {
-        e->capturing = 0;
-        e->capture_hint.clear();
+        end_capture_state(e);
         return WK_ERR_HIP;
     }
     int32_t rc = WK_OK;
     for (int i = 0; i < nplans && rc == WK_OK; i++) {
         e->capture_hint = hints[i];
+        e->capture_empty_after = empty_after[i];
         rc = wk_engine_submit(e, &plans[i]);
         if (rc == WK_OK && !e->light)
-            hipLaunchKernelGGL(k_publish_state, dim3(1), dim3(1), 0,
-                               e->stream, e->d_state, e->d_stats, e->h_pin);
+            launch_publish(e, empty_after[i] >= 0);
     }
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
-    e->capturing = 0;
-    e->capture_hint.clear();
+    end_capture_state(e);
     if (rc != WK_OK || ce != hipSuccess || !g) {
         if (g) (void)hipGraphDestroy(g);
         (void)stream_sync(e->stream);
@@ -2076,6 +2192,7 @@ extern "C" int32_t wk_engine_graph_build_suite(wk_engine_t *e,
     wg.nvars = e->nvars;
     wg.bound = e->bound;
     wg.light = e->light;
+    wg.view = e->tbl_view;
     e->graphs.push_back(std::move(wg));
     *gid = (int32_t)e->graphs.size() - 1;
     return WK_OK;
@@ -2090,6 +2207,7 @@ extern "C" int32_t wk_engine_graph_launch(wk_engine_t *e, int32_t gid) {
         return WK_ERR_STATE;
     if (hipGraphLaunch(e->graphs[gid].exec, e->stream) != hipSuccess)
         return WK_ERR_HIP;
+    e->zero_pending = false;  // the replay began with its own begin kernel
     return WK_OK;
 }
 
@@ -2111,6 +2229,7 @@ extern "C" int32_t wk_engine_graph_run(wk_engine_t *e, int32_t gid,
     wk_engine::wk_graph &g = e->graphs[gid];
     resolve_timing(e);
     if (hipGraphLaunch(g.exec, e->stream) != hipSuccess) return WK_ERR_HIP;
+    e->zero_pending = false;  // the replay began with its own begin kernel
     HIP_CHECK(stream_sync(e->stream));
     e->v2c = g.v2c;
     e->ncols = g.ncols;
@@ -2118,7 +2237,11 @@ extern "C" int32_t wk_engine_graph_run(wk_engine_t *e, int32_t gid,
     e->nvars = g.nvars;
     e->bound = g.bound;
     e->light = g.light;
-    if (e->h_pin[S_ERR]) return WK_ERR_CAP;
+    e->tbl_view = g.view;
+    if (e->h_pin[S_ERR]) {
+        e->h_pin[7] = 0;  // reported here, not to a later wk_engine_sync
+        return WK_ERR_CAP;
+    }
     e->nrows = (int64_t)e->h_pin[S_NROWS];
     if (nrows) *nrows = e->nrows;
     return WK_OK;

@@ -15,7 +15,11 @@ enum { PM_SIZE = 0,    // k2u: write edge count per row
        PM_EQ = 4 };    // k2c via reversed functional map: flag = (col == cval)
 
 // device query state (see engine): [0]=nrows [1]=scan total [2]=overflow
-// flag [3]=required rows; stats[0..6] = algorithmic bytes per category
+// flag [3]=required rows [4]=big-row queue length / scratch cursor
+// [5]=sticky guard-miss count of the optimistic (captured-graph)
+// kernels: zeroed only at query begin, turned into S_ERR by
+// k_publish_state [6]=input rows snapshot; stats[0..6] = algorithmic
+// bytes per category
 enum { S_NROWS = 0, S_TOTAL = 1, S_ERR = 2, S_REQ = 3, S_OVF = 4,
        S_DONE = 5, S_INROWS = 6, S_WORDS = 7 };
 enum { CAT_PROBE = 0, CAT_SCAN, CAT_EXPAND, CAT_FILTER, CAT_COPY, CAT_SPLIT,
@@ -64,7 +68,7 @@ __device__ __forceinline__ uint64_t csr_entry(const fnpage_t *__restrict__ pg,
 // (k_expand_in / k_expand_big): bitmap when present, else dense type_of.
 // The engine treats multi-type entities (type_of == 0xFFFF) in three
 // DELIBERATELY different ways — keep them apart:
-//   - here: a miss (-> S_DONE -> k_verify_commit -> S_ERR -> safe re-run)
+//   - here: a miss (-> S_DONE -> k_publish_state -> S_ERR -> safe re-run)
 //   - filter_keep: falls through to the hash probe
 //   - k_fn_gather: probes [v|TYPE|OUT]
 __device__ __forceinline__ bool typeof_nodrop_ok(

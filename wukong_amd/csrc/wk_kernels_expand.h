@@ -404,6 +404,15 @@ __global__ void k_set_state(uint64_t *__restrict__ d_state, uint64_t nrows) {
     d_state[S_OVF] = 0;
 }
 
+// query begin fused with the first state write: zero every state word
+// (S_ERR/S_REQ and the sticky S_DONE miss word included), then set the
+// start row count — one launch instead of k_zero_words + k_set_state
+__global__ void k_begin_state(uint64_t *__restrict__ d_state, uint64_t nrows) {
+#pragma unroll
+    for (int i = 0; i < S_WORDS; i++) d_state[i] = 0;
+    d_state[S_NROWS] = nrows;
+}
+
 // device projection to required-var columns (sparql.hpp:1510-1536)
 struct cols8 { int32_t c[8]; };
 __global__ void k_project(const sid_t *__restrict__ tbl, int ncols,
@@ -420,9 +429,21 @@ __global__ void k_project(const sid_t *__restrict__ tbl, int ncols,
     }
 }
 
-__global__ void k_publish_state(const uint64_t *__restrict__ d_state,
+// The optimistic kernels of a captured plan (k_expand_fn_map, the
+// verify-only k_filter_tpr, the verify-fused k_expand_in/_big) count
+// their guard misses into S_DONE, which nothing clears during a query;
+// the conversion to S_ERR happens ONCE, here, before the words are
+// copied out.  expect_empty (captured plans with a truncated empty
+// tail): the skipped patterns are only valid on an empty table, so any
+// row left raises S_ERR the same way.
+__global__ void k_publish_state(uint64_t *__restrict__ d_state,
                                 const uint64_t *__restrict__ d_stats,
-                                uint64_t *__restrict__ h_pin) {
+                                uint64_t *__restrict__ h_pin,
+                                int expect_empty) {
+    if (d_state[S_DONE] || (expect_empty && d_state[S_NROWS])) {
+        d_state[S_ERR] = 1;
+        d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
+    }
     for (int i = 0; i < S_WORDS; i++) h_pin[i] = d_state[i];
     for (int i = 0; i < CAT_COUNT; i++) h_pin[8 + i] = d_stats[i];
     // sticky error flag (h_pin slot 7): survives across back-to-back
@@ -440,7 +461,7 @@ __global__ void k_publish_state(const uint64_t *__restrict__ d_state,
 // verify-fused expansion (captured graphs only): when the NEXT pattern
 // is a no-drop `?v rdf:type CONST` filter on the NEW column (warm-pass
 // hint), each written value is checked inline (bitmap or dense type_of;
-// misses count into S_DONE -> k_verify_commit -> S_ERR -> safe re-run)
+// misses count into S_DONE -> k_publish_state -> S_ERR -> safe re-run)
 // and the separate full-table verify pass disappears.
 template <int NC>
 __global__ void k_expand_in(const sid_t *__restrict__ tbl, int ncols,
@@ -618,9 +639,11 @@ __global__ void k_fn_gather(const sid_t *__restrict__ tbl, int ncols,
 
 // OPTIMISTIC functional k2u: used ONLY inside captured graphs for
 // steps whose warm pass dropped no rows (store is immutable, so the
-// observation holds for replays; a miss at runtime still flips S_ERR
-// via k_commit_map and the caller falls back to the safe path).  The
-// 1:1 write needs no scan/compaction and coalesces perfectly.
+// observation holds for replays; a miss at runtime counts into the
+// sticky S_DONE word, k_publish_state turns it into S_ERR and the
+// caller falls back to the safe path).  The row count is unchanged, so
+// the step needs no commit; the 1:1 write needs no scan/compaction and
+// coalesces perfectly.
 template <int NC>
 __global__ void k_expand_fn_map(const sid_t *__restrict__ tbl,
                                 const fnpage_t *__restrict__ fn_pg,
@@ -662,29 +685,8 @@ __global__ void k_expand_fn_map(const sid_t *__restrict__ tbl,
         dst[NC] = tv;
     }
     if (miss)
-        atomicAdd((unsigned long long *)&d_state[S_OVF],
+        atomicAdd((unsigned long long *)&d_state[S_DONE],
                   (unsigned long long)miss);
-}
-
-// verify-fused expansion epilogue: any inline-typeof miss (S_DONE)
-// flips S_ERR so the replay is discarded and the safe path re-runs
-__global__ void k_verify_commit(uint64_t *__restrict__ d_state) {
-    if (d_state[S_DONE]) {
-        d_state[S_ERR] = 1;
-        d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
-        d_state[S_DONE] = 0;
-    }
-}
-
-// commit for the optimistic map: row count unchanged; any miss flags
-// S_ERR so the replay result is discarded and the safe path re-runs
-__global__ void k_commit_map(uint64_t *__restrict__ d_state) {
-    if (d_state[S_OVF]) {
-        d_state[S_ERR] = 1;
-        d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
-    }
-    d_state[S_TOTAL] = 0;
-    d_state[S_OVF] = 0;
 }
 
 __global__ void k_zero_words(uint64_t *p, int n) {

@@ -110,13 +110,14 @@ __global__ void k_filter_tpr(fparams P, int verify_only,
         if (verify_only) {
             // identity-verified filter (captured graphs): the warm pass
             // saw zero drops; every replay still checks every row and
-            // flags S_ERR on any miss (no writes, no table flip)
+            // counts misses into the sticky S_DONE word (-> S_ERR at
+            // the publish; no writes, no table flip, no commit)
             uint32_t miss = 0;
 #pragma unroll
             for (int k = 0; k < K; k++)
                 miss += (rr[k] < nrows && !keep[k]) ? 1u : 0u;
             if (miss)
-                atomicAdd((unsigned long long *)&d_state[S_OVF],
+                atomicAdd((unsigned long long *)&d_state[S_DONE],
                           (unsigned long long)miss);
             continue;
         }
