@@ -28,6 +28,10 @@
  *   k_csr_gather_tf, k_expand_tf[_big] — EXACT fused k2u + typeof
  *                       compaction over the CSR index (count pass ->
  *                       scan -> filtered write)
+ *   k_csr_gather_chain, k_expand_chain[_big] — the same exact pipeline
+ *                       with a per-row op chain (chain_t: fn-map
+ *                       lookups, bitmap type tests, equality tests of
+ *                       the FOLLOWING patterns) as the per-edge predicate
  *   k_scan_local/mid  — chunked exclusive scan with DEVICE-side length
  *                       (replaces the thrust scans, gpu_hash.cu:587-596);
  *                       k_scan_mid also commits the step (S_INROWS
@@ -227,6 +231,10 @@ struct wk_engine {
     bool hinting = false;  // graph-build hint pass: per-PATTERN row counts
                            // needed, so multi-step fusions are disabled
     int remote_step_idx = -1;  // pattern to run via the xGMI peer path
+    // a WHOLE plan is being run (wk_engine_submit / wk_engine_run_query,
+    // captures included): the only place multi-pattern op chains apply —
+    // the step API and UNION/OPTIONAL continuations keep per-pattern steps
+    bool whole_plan = false;
     // zero-copy i2u/c2u: the 1-col start table IS the (immutable) edge
     // list in the store — later steps read it in place instead of
     // replaying a 25-MB k_copy_list per query.  Cleared on every table
@@ -316,6 +324,14 @@ static hipEvent_t ev_get() { hipEvent_t e; (void)hipEventCreate(&e); return e; }
 // Read per call — bench.py flips it mid-process.
 static bool wk_fn_dispatch() {
     const char *v = getenv("WK_FN_DISPATCH");
+    return !(v && !atoi(v));
+}
+
+// WK_CHAIN=0: run every pattern as a step of its own (no per-row op
+// chain fused into an expansion).  Read per call, like
+// WK_FN_DISPATCH.
+static bool wk_chain() {
+    const char *v = getenv("WK_CHAIN");
     return !(v && !atoi(v));
 }
 
@@ -878,6 +894,117 @@ static const uint64_t *type_bitmap(const wk_engine *e, sid_t type_id) {
     return (e->gs && (size_t)type_id < e->gs->d_tbm.size())
                ? e->gs->d_tbm[type_id]
                : nullptr;
+}
+
+// functional map of (p, dir): pages (null = absent) and packed values
+static const fnpage_t *fn_map(const wk_engine *e, ssid_t p, int dir,
+                              const sid_t **vals) {
+    const size_t w = (size_t)p * 2 + dir;
+    if (!e->gs || w >= e->gs->d_fn_pages.size() || !e->gs->d_fn_pages[w])
+        return nullptr;
+    *vals = e->gs->d_fn_vals[w];
+    return e->gs->d_fn_pages[w];
+}
+
+// ---- per-row op chains -----------------------------
+struct chain_plan {
+    chain_t C{};
+    int npat = 0;             // patterns consumed (one op each)
+    int nfilter = 0;          // ops other than FN_APPEND
+    int out_cols = 0;         // column count after the chain
+    int nnew = 0;             // appended variables, in column order
+    ssid_t new_vars[CHAIN_MAX];
+    bool lone_typeof(int col) const {
+        return npat == 1 && C.op[0].kind == CH_TYPE && C.op[0].a == col;
+    }
+};
+
+// chains apply to whole-plan runs on the local, single-step-at-a-time
+// path only; off while the hint pass needs per-pattern row counts
+static bool chain_enabled(const wk_engine *e) {
+    return e->whole_plan && !e->hinting && !e->opt_mode &&
+           e->remote_step_idx < 0 && e->gs && wk_fn_dispatch() && wk_chain();
+}
+
+// Greedily collect the patterns from index `from` on that are per-row
+// ops over the layout (v2c, ncols): known subject, fixed predicate,
+// PK_NORMAL key, and the functional map / type bitmap the op reads is
+// built — the eligibility rules of step_filter / step_k2u_fn, one op per
+// pattern.  Stops at the first pattern that does not fit.  In a capture
+// with a truncated empty tail the chain never reaches into the tail.
+static void collect_chain(const wk_engine *e, int from,
+                          std::vector<int32_t> v2c, int ncols,
+                          chain_plan &cp) {
+    const wk_store *st = e->st;
+    cp.C.fn_base = st->fn_base;
+    cp.C.fn_n = st->fn_n;
+    cp.C.t_base = st->type_base;
+    cp.C.t_n = st->type_n;
+    int end = (int)e->pats.size();
+    if (e->capturing && e->capture_empty_after >= 0)
+        end = std::min(end, e->capture_empty_after + 1);
+    auto col_of = [&](ssid_t v) {
+        const int i = -(v + 1);
+        return (v < 0 && i < (int)v2c.size()) ? v2c[i] : -1;
+    };
+    for (int i = from; i < end && cp.npat < CHAIN_MAX; i++) {
+        const wk_pattern_t &pt = e->pats[i];
+        const ssid_t p = pt.predicate;
+        const int dir = pt.direction;
+        const int a = col_of(pt.subject);
+        if (a < 0 || p < 1) break;
+        if ((sid_t)p == TYPE_ID && dir == DIR_IN) break;  // PK_INDEX
+        chain_op op{nullptr, nullptr, 0, a, 0, 0};
+        const sid_t *vals = nullptr;
+        if (pt.object >= 0) {
+            if ((sid_t)p == TYPE_ID && dir == DIR_OUT) {
+                const uint64_t *tbm = type_bitmap(e, (sid_t)pt.object);
+                if (!tbm) break;
+                op.kind = CH_TYPE;
+                op.data = tbm;
+            } else {
+                // k2c: only the reversed-map form (host-resolved PM_EQ)
+                if (fn_map(e, p, dir, &vals) || st->nsrv != 1 ||
+                    !fn_map(e, p, dir ^ 1, &vals))
+                    break;
+                op.kind = CH_EQ;
+                op.cval = st->fn_get((size_t)p * 2 + (dir ^ 1),
+                                     (sid_t)pt.object);
+            }
+            cp.nfilter++;
+        } else if (col_of(pt.object) >= 0) {  // k2k
+            op.kind = CH_FN_EQ;
+            op.b = col_of(pt.object);
+            op.pg = fn_map(e, p, dir, &vals);
+            if (!op.pg && st->nsrv == 1) {  // reversed map: swap the roles
+                op.pg = fn_map(e, p, dir ^ 1, &vals);
+                std::swap(op.a, op.b);
+            }
+            if (!op.pg) break;
+            op.data = vals;
+            cp.nfilter++;
+        } else {  // functional k2u
+            const int oi = -(pt.object + 1);
+            if (oi >= (int)v2c.size() || ncols + 1 > e->cap_cols ||
+                ncols + 1 > ROW_MAX)
+                break;
+            op.pg = fn_map(e, p, dir, &vals);
+            if (!op.pg) break;
+            op.kind = CH_FN_APPEND;
+            op.data = vals;
+            v2c[oi] = ncols++;
+            cp.new_vars[cp.nnew++] = pt.object;
+        }
+        cp.C.op[cp.npat++] = op;
+    }
+    cp.C.nops = cp.npat;
+    cp.out_cols = ncols;
+}
+
+// bind a chain's appended variables to the columns from `first_col` on
+static void bind_chain_vars(wk_engine *e, const chain_plan &cp, int first_col) {
+    for (int j = 0; j < cp.nnew; j++)
+        e->v2c[-(cp.new_vars[j] + 1)] = first_col + j;
 }
 
 // End-of-step bookkeeping: bind new_var (a variable, < 0; 0 = none) to
@@ -1507,6 +1634,48 @@ static int32_t step_k2u_classic(wk_engine *e, const step_ctx &c,
     return WK_OK;
 }
 
+// The same exact pipeline with a per-row op chain as the per-edge
+// predicate: consumes the k2u and the chain's patterns.
+static int32_t step_k2u_chain(wk_engine *e, const step_ctx &c,
+                              const fnpage_t *c_pg, const chain_plan &cp) {
+    const wk_store *st = e->st;
+    const int G = scan_grid(e->bound);
+    const int nc_in = e->ncols;
+    // the edge value needs a column of its own (step_k2u checked cap_cols)
+    if (nc_in + 1 > ROW_MAX) return WK_ERR_STATE;
+    with_ncols(nc_in, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        if constexpr (NC < ROW_MAX) {
+            launch_gather_scan(e, G, /*timed*/ true, [&] {
+                hipLaunchKernelGGL(
+                    k_csr_gather_chain<NC>, dim3(grid_for(e->bound)),
+                    dim3(BLOCK), 0, e->stream, c.cur_tbl, c.col, c_pg,
+                    e->gs->d_csr_entries[(size_t)c.p * 2 + c.dir], st->fn_base,
+                    st->fn_n, e->d_edges, cp.C, e->d_state, e->d_stats,
+                    (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p);
+            });
+            TIME_BEGIN(e);
+            hipLaunchKernelGGL(
+                k_expand_chain<NC>, dim3(grid_for(e->bound)), dim3(BLOCK), 0,
+                e->stream, c.cur_tbl, e->d_edges, (uint64_t *)e->eoff.p,
+                (uint32_t *)e->cnt.p, (uint64_t *)e->prefix.p,
+                (uint64_t *)e->bsums.p, G, cp.C, cp.out_cols, e->d_state,
+                (uint64_t)e->cap_rows, e->d_stats, (uint32_t *)e->ovf.p,
+                c.out_tbl);
+            hipLaunchKernelGGL(
+                k_expand_chain_big<NC>, dim3(512), dim3(BLOCK), 0, e->stream,
+                c.cur_tbl, e->d_edges, (uint64_t *)e->eoff.p,
+                (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p, G, cp.C,
+                cp.out_cols, e->d_state, (uint64_t)e->cap_rows,
+                (uint32_t *)e->ovf.p, c.out_tbl);
+            TIME_END(e, CAT_EXPAND);
+        }
+    });
+    bind_chain_vars(e, cp, nc_in + 1);
+    finish_step(e, c.o, cp.out_cols, e->cap_rows, 1 + cp.npat);
+    return WK_OK;
+}
+
 // known_to_unknown: pick the pipeline (fn map, exact typeof-fused CSR,
 // classic)
 static int32_t step_k2u(wk_engine *e, const step_ctx &c) {
@@ -1533,6 +1702,16 @@ static int32_t step_k2u(wk_engine *e, const step_ctx &c) {
     const bool tf_deg_ok =
         w_seg < st->seg_keys.size() && st->seg_keys[w_seg] &&
         st->seg_edges[w_seg] / st->seg_keys[w_seg] <= 32;
+    // a trailing chain that does more than the lone typeof filter (whose
+    // two paths below are both measured) rides on the exact pipeline
+    if (c_pg && tf_deg_ok && st->nsrv == 1 && chain_enabled(e)) {
+        chain_plan cp;
+        std::vector<int32_t> v2c = e->v2c;
+        v2c[-(c.o + 1)] = e->ncols;
+        collect_chain(e, e->step + 1, v2c, e->ncols + 1, cp);
+        if (cp.nfilter && !cp.lone_typeof(e->ncols))
+            return step_k2u_chain(e, c, c_pg, cp);
+    }
     if (c_pg && tf_deg_ok && st->nsrv == 1 && !e->hinting &&
         !hint_nodrop(e, e->step + 1)) {
         const sid_t t = typeof_lookahead(e, c.o);
@@ -1943,6 +2122,27 @@ static int32_t skip_empty_tail(wk_engine *e) {
     return WK_OK;
 }
 
+// The main pattern list from the current step to its end, as a WHOLE
+// plan: op chains may span patterns (whole_plan is set for exactly this
+// scope, whatever path leaves it).
+static int32_t run_whole_plan(wk_engine *e) {
+    struct scope {
+        wk_engine *e;
+        explicit scope(wk_engine *e_) : e(e_) { e->whole_plan = true; }
+        ~scope() { e->whole_plan = false; }
+    } guard(e);
+    while (e->step < (int)e->pats.size()) {
+        // captured plan with an empty tail: nothing is launched for the
+        // patterns the warm pass saw run on zero rows
+        if (e->capturing && e->capture_empty_after >= 0 &&
+            e->step > e->capture_empty_after)
+            return skip_empty_tail(e);
+        int32_t rc = exec_pattern(e);
+        if (rc) return rc;
+    }
+    return WK_OK;
+}
+
 // asynchronous whole-plan submission: enqueue the full launch chain and
 // return without any sync (pipelined multi-engine execution — the
 // reference proxy's in-flight window, proxy.hpp:477-525)
@@ -1988,16 +2188,7 @@ extern "C" int32_t wk_engine_submit(wk_engine_t *e, const wk_plan_t *plan) {
         e->step = 2;
         return WK_OK;
     }
-    while (e->step < (int)e->pats.size()) {
-        // captured plan with an empty tail: nothing is launched for the
-        // patterns the warm pass saw run on zero rows
-        if (e->capturing && e->capture_empty_after >= 0 &&
-            e->step > e->capture_empty_after)
-            return skip_empty_tail(e);
-        rc = exec_pattern(e);
-        if (rc) return rc;
-    }
-    return WK_OK;
+    return run_whole_plan(e);
 }
 
 // WK_FORCE_EMPTY_HINT=<k> (test-only, read at graph build): assume the
@@ -2542,10 +2733,8 @@ extern "C" int32_t wk_engine_run_query(wk_engine_t *e, const wk_plan_t *plan,
     for (int attempt = 0; attempt < 6; attempt++) {
         int32_t rc = wk_engine_begin_query(e, plan);
         if (rc) return rc;
-        while (e->step < (int)e->pats.size()) {
-            rc = exec_pattern(e);
-            if (rc) return rc;
-        }
+        rc = run_whole_plan(e);
+        if (rc) return rc;
         // UNION then OPTIONAL, the reference's order
         // (execute_sparql_query, sparql.hpp:1564-1662)
         if (plan->nunion > 0 && plan->union_pats && plan->union_sizes) {

@@ -80,6 +80,77 @@ __device__ __forceinline__ bool typeof_nodrop_ok(
     return t != 0xFFFF && (sid_t)t == cval;
 }
 
+// ---------------------------------------------------------------------
+// Per-row op chain: a run of consecutive 1:1 patterns
+// (functional-map lookups, bitmap type tests, equality tests) evaluated
+// on ONE register-resident row.  Passed by value like fparams; the host
+// collector (collect_chain, gpu_engine.hip) has already resolved every
+// map, bitmap, column and constant, and normalised a reversed-map k2k to
+// (key col, value col).
+// ---------------------------------------------------------------------
+enum { CH_FN_APPEND = 0,  // v = fn[row[a]]; 0 drops, else append v
+       CH_TYPE = 1,       // bitmap bit of row[a] (exact, multi-type incl.)
+       CH_FN_EQ = 2,      // fn[row[a]] != 0 && == row[b]   (k2k)
+       CH_EQ = 3 };       // row[a] == cval                 (PM_EQ k2c)
+constexpr int CHAIN_MAX = 8;  // ops per chain
+constexpr int ROW_MAX = 8;    // wk_engine_begin_query rejects nvars > 8
+
+struct chain_op {
+    const fnpage_t *pg;  // FN_*: map pages
+    const void *data;    // FN_*: packed values; TYPE: membership bitmap
+    int32_t kind, a, b;
+    sid_t cval;
+};
+struct chain_t {
+    chain_op op[CHAIN_MAX];
+    uint64_t fn_base, fn_n, t_base, t_n;
+    int32_t nops;
+};
+
+// Column access by a (wave-uniform) runtime index as select chains: a
+// runtime-indexed local array would spill to scratch (HIP guide rule 20)
+__device__ __forceinline__ sid_t row_get(const sid_t (&row)[ROW_MAX], int c) {
+    sid_t v = row[0];
+#pragma unroll
+    for (int i = 1; i < ROW_MAX; i++) v = (c == i) ? row[i] : v;
+    return v;
+}
+__device__ __forceinline__ void row_set(sid_t (&row)[ROW_MAX], int c, sid_t v) {
+#pragma unroll
+    for (int i = 0; i < ROW_MAX; i++) row[i] = (c == i) ? v : row[i];
+}
+
+// Evaluate the chain on a row whose first NC columns are valid; appended
+// columns land at NC, NC+1, ...  Returns keep/drop, stops at the first
+// failing op.
+template <int NC>
+__device__ __forceinline__ bool chain_eval(const chain_t &C,
+                                           sid_t (&row)[ROW_MAX]) {
+    int nc = NC;
+#pragma unroll
+    for (int i = 0; i < CHAIN_MAX; i++) {
+        if (i >= C.nops) break;
+        const chain_op &o = C.op[i];
+        const sid_t v = row_get(row, o.a);
+        if (o.kind == CH_TYPE) {
+            if (!tbm_has((const uint64_t *)o.data, C.t_base, C.t_n, v))
+                return false;
+        } else if (o.kind == CH_EQ) {
+            if (v != o.cval) return false;
+        } else {
+            const sid_t tv = fn_lookup(o.pg, (const sid_t *)o.data, C.fn_base,
+                                       C.fn_n, v);
+            if (!tv) return false;
+            if (o.kind == CH_FN_EQ) {
+                if (tv != row_get(row, o.b)) return false;
+            } else {
+                row_set(row, nc++, tv);
+            }
+        }
+    }
+    return true;
+}
+
 // one cluster-hash lookup: walk the bucket chain, 7 slot compares per
 // 128-B bucket (gstore.hpp:341-361 semantics)
 __device__ __forceinline__ void probe_one(const vertex_t *__restrict__ verts,

@@ -278,6 +278,162 @@ __global__ void k_expand_tf_big(const sid_t *__restrict__ tbl, int ncols,
     }
 }
 
+// The same exact count -> scan -> emit pipeline with a per-row op chain
+// (wk_kernels_common.h chain_t) as the per-edge
+// predicate: the candidate row is the NC-column input row plus the edge
+// value, the chain tests it (and may append further columns), d_cnt gets
+// the number of PASSING edges.  Siblings of the typeof-only kernels
+// above, which stay as they are (both of their paths are measured).
+template <int NC>
+__global__ void k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
+                                   const fnpage_t *__restrict__ pg,
+                                   const uint64_t *__restrict__ entries,
+                                   uint64_t base, uint64_t n,
+                                   const sid_t *__restrict__ edges,
+                                   chain_t C,
+                                   const uint64_t *__restrict__ d_state,
+                                   uint64_t *__restrict__ d_stats,
+                                   uint64_t *__restrict__ d_eoff,
+                                   uint32_t *__restrict__ d_cnt)
+{
+    static_assert(NC < ROW_MAX, "the edge value needs a column");
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 * NC + 16 + 8 + 12));
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
+        sid_t row[ROW_MAX];
+#pragma unroll
+        for (int c = 0; c < ROW_MAX; c++) row[c] = 0;
+#pragma unroll
+        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
+        const uint64_t e =
+            csr_entry(pg, entries, base, n, row_get(row, col));
+        const uint64_t off = csr_off(e);
+        const uint32_t len = csr_len(e);
+        uint32_t keep = 0;
+        for (uint32_t k = 0; k < len; k++) {
+            row[NC] = edges[off + k];
+            keep += chain_eval<NC + 1>(C, row) ? 1u : 0u;
+        }
+        d_eoff[r] = e;  // {off:40|len:24} for the writer's re-walk
+        d_cnt[r] = keep;
+    }
+}
+
+// writer: re-walk, re-evaluate, emit the passing (widened) rows at the
+// exact scanned positions; rows with > 32 edges go to the wave pass
+template <int NC>
+__global__ void k_expand_chain(const sid_t *__restrict__ tbl,
+                               const sid_t *__restrict__ edges,
+                               const uint64_t *__restrict__ d_eoff,
+                               const uint32_t *__restrict__ d_cnt,
+                               const uint64_t *__restrict__ d_pre,
+                               const uint64_t *__restrict__ bsums, int G,
+                               chain_t C, int oc,
+                               uint64_t *__restrict__ d_state, uint64_t cap,
+                               uint64_t *__restrict__ d_stats,
+                               uint32_t *__restrict__ ovf,
+                               sid_t *__restrict__ out)
+{
+    static_assert(NC < ROW_MAX, "the edge value needs a column");
+    const int64_t nrows = (int64_t)d_state[S_INROWS];
+    const int64_t chunk = (nrows + G - 1) / G;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows;
+         r += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t keep = d_cnt[r];
+        if (!keep) continue;
+        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        if (basep >= cap) continue;
+        const uint64_t e = d_eoff[r];
+        const uint64_t off = csr_off(e);
+        const uint32_t len = csr_len(e);
+        if (len > 32) {
+            unsigned long long i = atomicAdd(
+                (unsigned long long *)&d_state[S_OVF], 1ull);
+            ovf[i] = (uint32_t)r;
+            continue;
+        }
+        sid_t row[ROW_MAX];
+#pragma unroll
+        for (int c = 0; c < ROW_MAX; c++) row[c] = 0;
+#pragma unroll
+        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
+        sid_t *dst = out + (int64_t)basep * oc;
+        uint32_t w = 0;
+        for (uint32_t k = 0; k < len && w < keep; k++) {
+            row[NC] = edges[off + k];
+            if (!chain_eval<NC + 1>(C, row)) continue;
+            if (basep + w >= cap) break;
+#pragma unroll
+            for (int c = 0; c < ROW_MAX; c++)
+                if (c < oc) dst[c] = row[c];
+            dst += oc;
+            w++;
+        }
+    }
+    // written rows + per-input-row scan words (the walk itself is counted
+    // by the gather)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        atomicAdd((unsigned long long *)&d_stats[CAT_EXPAND],
+                  (unsigned long long)(d_state[S_NROWS] * (4 * oc) +
+                                       (uint64_t)nrows * 20));
+}
+
+template <int NC>
+__global__ void k_expand_chain_big(const sid_t *__restrict__ tbl,
+                                   const sid_t *__restrict__ edges,
+                                   const uint64_t *__restrict__ d_eoff,
+                                   const uint64_t *__restrict__ d_pre,
+                                   const uint64_t *__restrict__ bsums, int G,
+                                   chain_t C, int oc,
+                                   const uint64_t *__restrict__ d_state,
+                                   uint64_t cap,
+                                   const uint32_t *__restrict__ ovf,
+                                   sid_t *__restrict__ out)
+{
+    static_assert(NC < ROW_MAX, "the edge value needs a column");
+    const int64_t nq = (int64_t)d_state[S_OVF];
+    const int64_t nrows = (int64_t)d_state[S_INROWS];
+    const int64_t chunk = (nrows + G - 1) / G;
+    const int lane = threadIdx.x & 63;
+    const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t q = w0; q < nq; q += nw) {
+        const int64_t r = ovf[q];
+        const uint64_t e = d_eoff[r];
+        const uint64_t off = csr_off(e);
+        const uint32_t len = csr_len(e);
+        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        if (basep >= cap) continue;
+        sid_t row[ROW_MAX];
+#pragma unroll
+        for (int c = 0; c < ROW_MAX; c++) row[c] = 0;
+#pragma unroll
+        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
+        uint64_t wbase = 0;  // passing-rank base across 64-edge chunks
+        for (uint32_t k0 = 0; k0 < len; k0 += 64) {
+            const uint32_t k = k0 + lane;
+            bool pass = false;
+            if (k < len) {
+                row[NC] = edges[off + k];
+                pass = chain_eval<NC + 1>(C, row);
+            }
+            uint64_t mask = __ballot(pass);
+            if (pass) {
+                uint64_t pos = basep + wbase +
+                               (uint64_t)__popcll(mask & ((1ull << lane) - 1));
+                if (pos < cap) {
+                    sid_t *dst = out + (int64_t)pos * oc;
+#pragma unroll
+                    for (int c = 0; c < ROW_MAX; c++)
+                        if (c < oc) dst[c] = row[c];
+                }
+            }
+            wbase += (uint64_t)__popcll(mask);
+        }
+    }
+}
+
 // chunked exclusive prefix of d_cnt -> d_pre + per-chunk sums (same
 // chunk math as k_probe_scan so the expansion kernels are unchanged)
 __global__ void k_scan_local(const uint32_t *__restrict__ d_cnt,
