@@ -33,6 +33,22 @@ typedef struct {
     int32_t   direction;  /* WK_DIR_IN / WK_DIR_OUT */
 } wk_pattern_t;
 
+/* One postfix node of a plan's FILTER program (wk_plan_t.filter).  Ids
+ * compare verbatim (the id<->string map is a bijection, so
+ * relational_filter's string equality, core/engine/sparql.hpp:1183-1196,
+ * IS id equality); BLANK_ID is an ordinary value. */
+enum {
+    WK_F_EQ = 1,    /* push a == b; operand < 0 variable, > 0 constant sid */
+    WK_F_NE = 2,    /* push a != b                                         */
+    WK_F_BOUND = 3, /* push a != BLANK_ID (bound_filter, :1228-1240)       */
+    WK_F_AND = 4,   /* pop 2, push x && y (general_filter, :1323-1360)     */
+    WK_F_OR = 5,    /* pop 2, push x || y                                  */
+    WK_F_NOT = 6    /* plain negation (the reference's general_filter
+                     * rejects its own Filter::Type::Not)                  */
+};
+#define WK_FILTER_MAX 32
+typedef struct { int32_t op, a, b; } wk_fnode_t;
+
 /* A full query plan — the planner-ordered pattern list plus the final
  * projection (core/query.hpp required_vars/distinct/limit,
  * core/engine/sparql.hpp:1424-1551). */
@@ -63,6 +79,17 @@ typedef struct {
     const wk_pattern_t *union_pats;
     const int32_t *union_sizes;
     int32_t   nunion;
+    /* FILTER (pattern_group.filters, core/query.hpp:118-138; stage 4 of
+     * execute_sparql_query, core/engine/sparql.hpp:1651-1655,
+     * execute_filter :1362-1382): the ID-exact subset as ONE postfix
+     * program, every FILTER clause ANDed in.  NULL/0 when absent; kept at
+     * the END of the struct so zero-initialised plans stay valid.
+     * wk_engine_begin_query returns WK_ERR_PLAN for an unknown op, a
+     * variable outside -1..-nvars, an operand 0, stack underflow, a final
+     * stack depth other than 1, more than WK_FILTER_MAX nodes, or a
+     * variable that no pattern of the plan (main, union, optional) binds. */
+    const wk_fnode_t *filter;
+    int32_t   nfilter;
 } wk_plan_t;
 
 /* A materialised binding table (SPARQLQuery::Result subset —
@@ -172,7 +199,8 @@ int32_t wk_engine_submit_light_batch(wk_engine_t *, const int64_t *subj,
  * emulator's multi-pattern templates A4/A6.  consts[i] replaces
  * patterns[0].subject.  Blind replies only; a query whose table
  * outgrows LDS reports count UINT64_MAX and must be re-run on the
- * per-pattern path.  WK_ERR_PLAN = template shape not interpretable. */
+ * per-pattern path.  WK_ERR_PLAN = template shape not interpretable, or
+ * the template carries a FILTER (the interpreter evaluates none). */
 int32_t wk_engine_submit_plan_batch(wk_engine_t *, const wk_plan_t *tmpl,
                                     const int64_t *consts, int32_t n);
 /* Blocks until the window completes; fills the n per-query row counts
@@ -233,6 +261,13 @@ int32_t wk_engine_col_num(const wk_engine_t *);
  * one-sided RDMA, gstore.hpp:260-338).  Advances the step. */
 int32_t wk_engine_execute_filter_list(wk_engine_t *, const wk_sid_t *sorted_list,
                                       uint64_t n, int64_t *nrows_out);
+/* Run the CURRENT plan's whole FILTER program on the current table
+ * (execute_filter, sparql.hpp:1362-1382).  The step API never pushes a
+ * filter down: the caller decides when every referenced variable has a
+ * column (WK_ERR_PLAN otherwise).  nrows_out = NULL launches
+ * asynchronously, as for filter pattern steps.  A plan without a filter
+ * is a no-op. */
+int32_t wk_engine_execute_filter(wk_engine_t *, int64_t *nrows_out);
 
 /* ---- xGMI peer mappings (small-table remote reads) ------------------
  * The reference reads sub-threshold tables' remote edge lists in place

@@ -25,6 +25,52 @@ class WkPattern(ctypes.Structure):
                 ("object", ctypes.c_int32), ("direction", ctypes.c_int32)]
 
 
+class WkFNode(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int32), ("a", ctypes.c_int32),
+                ("b", ctypes.c_int32)]
+
+
+#: FILTER ops (wukong_abi.h WK_F_*): name -> (code, operands, sub-expressions)
+FILTER_OPS = {"eq": (1, 2, 0), "ne": (2, 2, 0), "bound": (3, 1, 0),
+              "and": (4, 0, 2), "or": (5, 0, 2), "not": (6, 0, 1)}
+FILTER_MAX = 32
+
+
+def _filter_postfix(expr, nvars, out):
+    """Append the postfix form of one nested-tuple FILTER expression to
+    `out` as (op, a, b) triples, validating op names, arity and operand
+    ranges on the way."""
+    if not isinstance(expr, (tuple, list)) or not expr \
+            or not isinstance(expr[0], str):
+        raise ValueError(f"bad filter expression {expr!r}")
+    name = expr[0]
+    if name not in FILTER_OPS:
+        raise ValueError(f"unknown filter op {name!r}")
+    code, nopnd, nsub = FILTER_OPS[name]
+    if len(expr) != 1 + nopnd + nsub:
+        raise ValueError(f"filter op {name!r} takes {nopnd + nsub} "
+                         f"argument(s), got {len(expr) - 1}")
+    if nsub:
+        for sub in expr[1:]:
+            _filter_postfix(sub, nvars, out)
+        out.append((code, 0, 0))
+        return
+    opnds = []
+    for v in expr[1:]:
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"filter operand {v!r} is not an id")
+        v = int(v)
+        if v < -nvars:
+            raise ValueError(f"variable {v} out of range for nvars={nvars}")
+        if v == 0 or v >= (1 << 31):
+            raise ValueError(f"filter operand {v} is neither a variable "
+                             "nor a constant id")
+        opnds.append(v)
+    if name == "bound" and opnds[0] > 0:
+        raise ValueError("bound() takes a variable")
+    out.append((code, opnds[0], opnds[1] if nopnd == 2 else 0))
+
+
 class WkPlan(ctypes.Structure):
     _fields_ = [("patterns", ctypes.POINTER(WkPattern)),
                 ("npatterns", ctypes.c_int32),
@@ -40,7 +86,10 @@ class WkPlan(ctypes.Structure):
                 ("nopt", ctypes.c_int32),
                 ("union_pats", ctypes.POINTER(WkPattern)),
                 ("union_sizes", ctypes.POINTER(ctypes.c_int32)),
-                ("nunion", ctypes.c_int32)]
+                ("nunion", ctypes.c_int32),
+                # FILTER postfix program (wukong_abi.h wk_fnode_t)
+                ("filter", ctypes.POINTER(WkFNode)),
+                ("nfilter", ctypes.c_int32)]
 
 
 class WkResult(ctypes.Structure):
@@ -116,6 +165,8 @@ _eng_step_remote = _sig("wk_engine_execute_one_pattern_remote", c_i32,
                         [c_vp, ctypes.POINTER(c_i64)])
 _eng_row_count = _sig("wk_engine_row_count", c_i32,
                       [c_vp, ctypes.POINTER(c_i64)])
+_eng_exec_filter = _sig("wk_engine_execute_filter", c_i32,
+                        [c_vp, ctypes.POINTER(c_i64)])
 
 
 class WkPeerBlob(ctypes.Structure):
@@ -210,7 +261,8 @@ class Plan:
     """A planner-ordered pattern list (vars negative: -1..-nvars)."""
 
     def __init__(self, patterns, nvars, required_vars, distinct=False,
-                 limit=-1, offset=0, blind=False, optional=None, unions=None):
+                 limit=-1, offset=0, blind=False, optional=None, unions=None,
+                 filters=None):
         self.patterns = list(patterns)
         self.nvars = nvars
         self.required_vars = list(required_vars)
@@ -220,6 +272,20 @@ class Plan:
         self.blind = blind
         self.optional = list(optional or [])   # OPTIONAL pattern group
         self.unions = [list(u) for u in (unions or [])]  # UNION branches
+        # FILTER clauses, ANDed: nested tuples over ("eq"|"ne", a, b),
+        # ("bound", v), ("and"|"or", x, y), ("not", x); operands < 0 are
+        # variables, > 0 constant ids.  Validated here like the patterns;
+        # the postfix program (wk_plan_t.filter) holds at most 32 nodes.
+        self.filters = list(filters or [])
+        self._filter_nodes = []
+        for k, f in enumerate(self.filters):
+            _filter_postfix(f, nvars, self._filter_nodes)
+            if k:
+                self._filter_nodes.append((FILTER_OPS["and"][0], 0, 0))
+        if len(self._filter_nodes) > FILTER_MAX:
+            raise ValueError(
+                f"filter program has {len(self._filter_nodes)} nodes "
+                f"(max {FILTER_MAX})")
         # validate var ids HERE: an out-of-range var (< -nvars) would
         # index past the engine's v2c array on the C side
         all_pats = (self.patterns + self.optional
@@ -262,6 +328,12 @@ class Plan:
             plan.union_sizes = ctypes.cast(us, ctypes.POINTER(ctypes.c_int32))
             plan.nunion = len(self.unions)
             plan._keepalive.extend((up, us))
+        if self._filter_nodes:
+            fn = (WkFNode * len(self._filter_nodes))(
+                *[WkFNode(*t) for t in self._filter_nodes])
+            plan.filter = ctypes.cast(fn, ctypes.POINTER(WkFNode))
+            plan.nfilter = len(self._filter_nodes)
+            plan._keepalive.append(fn)
         return plan
 
 
@@ -607,6 +679,19 @@ class Engine:
         if rc != 0:
             raise RuntimeError(f"execute_filter_list rc={rc}")
         return n.value
+
+    def execute_filter(self, sync=True):
+        """Run the current plan's whole FILTER program on the current
+        table (step API: no pushdown — call it once every referenced
+        variable has a column; ValueError otherwise).  Returns the row
+        count, or None with sync=False (resolve with row_count())."""
+        n = c_i64()
+        rc = _eng_exec_filter(self._h, ctypes.byref(n) if sync else None)
+        if rc == -3:
+            raise ValueError("filter references a variable with no column")
+        if rc != 0:
+            raise RuntimeError(f"execute_filter rc={rc}")
+        return n.value if sync else None
 
     @property
     def pattern_step(self):

@@ -154,6 +154,122 @@ __global__ void k_filter_tpr(fparams P, int verify_only,
 }
 
 // ---------------------------------------------------------------------
+// FILTER expressions (execute_filter, sparql.hpp:
+// 1362-1382): the ID-exact subset =, !=, bound, &&, ||, ! as a postfix
+// program over the row's columns.  The host (gpu_engine.hip) has
+// validated the program and resolved every variable to its column: an
+// operand is a column (ca/cb >= 0) or a constant (va/vb).  Ids compare
+// verbatim, BLANK_ID included.
+// ---------------------------------------------------------------------
+struct fnode_d {
+    int32_t op;      // WK_F_*
+    int32_t ca, cb;  // operand columns, -1 = constant
+    sid_t va, vb;    // constant operands
+};
+struct fprog_t {
+    fnode_d node[WK_FILTER_MAX];
+    const sid_t *tbl;
+    int32_t n, ncols;
+    uint32_t bytes_per_row;  // 4 * distinct operand columns + 8 * ncols
+};
+
+// Same tile, ranks and cursor discipline as k_filter_tpr (5g(ii)); the
+// keep decision is the program.  The program sits in the kernel-argument
+// segment and is walked with a wave-uniform index; the evaluation stack
+// of each of the thread's K rows is a bit-stack in one 32-bit register
+// (a valid program of <= 32 nodes never holds more than 16 values), and
+// operands come straight from the table — no runtime-indexed local
+// array, no scratch.
+__global__ void k_filter_expr(fprog_t P, uint64_t *__restrict__ d_state,
+                              uint64_t *__restrict__ d_stats,
+                              sid_t *__restrict__ out_tbl)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * P.bytes_per_row);
+    constexpr int K = 4;
+    __shared__ unsigned long long s_base;
+    __shared__ unsigned int s_cnt;
+    __shared__ unsigned int s_wbase[SCAN_T / 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const int ncols = P.ncols;
+    const sid_t *__restrict__ tbl = P.tbl;
+    const int64_t tile = (int64_t)blockDim.x * K;
+    const int64_t stride = (int64_t)gridDim.x * tile;
+
+    for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows; base += stride) {
+        const int64_t r0 = base + threadIdx.x;
+        const int64_t r1 = r0 + SCAN_T, r2 = r1 + SCAN_T, r3 = r2 + SCAN_T;
+        const bool in0 = r0 < nrows, in1 = r1 < nrows, in2 = r2 < nrows,
+                   in3 = r3 < nrows;
+        const sid_t *row0 = tbl + r0 * ncols, *row1 = tbl + r1 * ncols,
+                    *row2 = tbl + r2 * ncols, *row3 = tbl + r3 * ncols;
+        uint32_t st0 = 0, st1 = 0, st2 = 0, st3 = 0;
+        for (int i = 0; i < P.n; i++) {
+            const int op = P.node[i].op;
+            if (op <= WK_F_BOUND) {
+                const int ca = P.node[i].ca, cb = P.node[i].cb;
+                const sid_t va = P.node[i].va;
+                const sid_t vb = (op == WK_F_BOUND) ? BLANK_ID : P.node[i].vb;
+                // rows past the end read nothing and are dropped below
+                const sid_t a0 = (ca >= 0 && in0) ? row0[ca] : va;
+                const sid_t a1 = (ca >= 0 && in1) ? row1[ca] : va;
+                const sid_t a2 = (ca >= 0 && in2) ? row2[ca] : va;
+                const sid_t a3 = (ca >= 0 && in3) ? row3[ca] : va;
+                const sid_t b0 = (cb >= 0 && in0) ? row0[cb] : vb;
+                const sid_t b1 = (cb >= 0 && in1) ? row1[cb] : vb;
+                const sid_t b2 = (cb >= 0 && in2) ? row2[cb] : vb;
+                const sid_t b3 = (cb >= 0 && in3) ? row3[cb] : vb;
+                // EQ pushes a == b; NE and BOUND (b = BLANK_ID) push a != b
+                const uint32_t inv = (op == WK_F_EQ) ? 0u : 1u;
+                st0 = (st0 << 1) | ((uint32_t)(a0 == b0) ^ inv);
+                st1 = (st1 << 1) | ((uint32_t)(a1 == b1) ^ inv);
+                st2 = (st2 << 1) | ((uint32_t)(a2 == b2) ^ inv);
+                st3 = (st3 << 1) | ((uint32_t)(a3 == b3) ^ inv);
+            } else if (op == WK_F_AND) {
+                st0 = (st0 >> 1) & (st0 | ~1u);
+                st1 = (st1 >> 1) & (st1 | ~1u);
+                st2 = (st2 >> 1) & (st2 | ~1u);
+                st3 = (st3 >> 1) & (st3 | ~1u);
+            } else if (op == WK_F_OR) {
+                st0 = (st0 >> 1) | (st0 & 1u);
+                st1 = (st1 >> 1) | (st1 & 1u);
+                st2 = (st2 >> 1) | (st2 & 1u);
+                st3 = (st3 >> 1) | (st3 & 1u);
+            } else {  // WK_F_NOT
+                st0 ^= 1u; st1 ^= 1u; st2 ^= 1u; st3 ^= 1u;
+            }
+        }
+        const bool keep0 = in0 && (st0 & 1u), keep1 = in1 && (st1 & 1u),
+                   keep2 = in2 && (st2 & 1u), keep3 = in3 && (st3 & 1u);
+        if (threadIdx.x == 0) s_cnt = 0;
+        __syncthreads();
+        const uint64_t m0 = __ballot(keep0), m1 = __ballot(keep1),
+                       m2 = __ballot(keep2), m3 = __ballot(keep3);
+        const uint32_t c0 = (uint32_t)__popcll(m0), c1 = (uint32_t)__popcll(m1),
+                       c2 = (uint32_t)__popcll(m2), c3 = (uint32_t)__popcll(m3);
+        if (lane == 0) s_wbase[wid] = atomicAdd(&s_cnt, c0 + c1 + c2 + c3);
+        __syncthreads();
+        if (threadIdx.x == 0)
+            s_base = s_cnt ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
+                                       (unsigned long long)s_cnt)
+                           : 0;
+        __syncthreads();
+        const uint64_t below = (1ull << lane) - 1;
+        const uint64_t wpos = s_base + s_wbase[wid];
+        auto emit = [&](bool keep, uint64_t pos, const sid_t *srow) {
+            if (!keep) return;
+            sid_t *dst = out_tbl + (int64_t)pos * ncols;
+            for (int c = 0; c < ncols; c++) dst[c] = srow[c];
+        };
+        emit(keep0, wpos + (uint32_t)__popcll(m0 & below), row0);
+        emit(keep1, wpos + c0 + (uint32_t)__popcll(m1 & below), row1);
+        emit(keep2, wpos + c0 + c1 + (uint32_t)__popcll(m2 & below), row2);
+        emit(keep3, wpos + c0 + c1 + c2 + (uint32_t)__popcll(m3 & below), row3);
+    }
+}
+
+// ---------------------------------------------------------------------
 // VERSATILE predicate-variable ops (sparql.hpp:556-744): one kernel
 // covers known/const_unknown_unknown (append p [, y] columns) and
 // known/const_unknown_const (keep one row per matching p).  Block per

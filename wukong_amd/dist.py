@@ -186,6 +186,29 @@ class DistQuery:
         optional = getattr(plan, "optional", [])
         if optional:
             self._run_optional(optional)
+        if getattr(plan, "filters", None):
+            self._run_filters(plan.filters)
+
+    def _run_filters(self, filters):
+        """FILTER, the reference's stage 4 (execute_filter,
+        sparql.hpp:1362-1382 under :1651-1655): row-local, so every rank
+        filters its own rows and nothing is exchanged.  On the device
+        when the final table lives in an engine that offers
+        execute_filter; the host-side union parts and optional table go
+        through the numpy evaluator."""
+        if getattr(self, "_opt_table", None) is not None:
+            self._opt_table = filter_rows(self._opt_table, self._opt_v2c,
+                                          filters)
+        elif getattr(self, "_union_parts", None) is not None:
+            self._union_parts = [filter_rows(t, self._union_v2c, filters)
+                                 for t in self._union_parts]
+        elif hasattr(self.ex, "execute_filter"):
+            self.ex.execute_filter()
+        else:
+            v2c, _ = self.states[-1]
+            self.ex.rows()
+            kept = filter_rows(np.asarray(self.ex.table()), v2c, filters)
+            self.ex.load(kept, v2c, len(self.plan.patterns))
 
     def _run_unions(self, unions, local_var):
         """UNION branches, distributed: each branch inherits the merged
@@ -459,6 +482,45 @@ class DistQuery:
         return final_process(full, v2c, p)
 
 
+def filter_rows(table, v2c, filters):
+    """Rows of a host table that pass every FILTER clause (the Plan
+    `filters` nested tuples).  Ids compare verbatim, BLANK included —
+    the engine's k_filter_expr semantics, restated over numpy columns."""
+    t = np.asarray(table)
+    if t.ndim != 2 or not len(t):
+        return t
+    blank = np.uint32(DistQuery.BLANK)
+
+    def opnd(x):
+        if x > 0:
+            return np.uint32(x)
+        col = v2c[-(x + 1)] if -(x + 1) < len(v2c) else -1
+        if col < 0:
+            raise ValueError(f"filter variable {x} has no column")
+        return t[:, col]
+
+    def ev(e):
+        op = e[0]
+        if op == "eq":
+            return opnd(e[1]) == opnd(e[2])
+        if op == "ne":
+            return opnd(e[1]) != opnd(e[2])
+        if op == "bound":
+            return opnd(e[1]) != blank
+        if op == "not":
+            return ~ev(e[1])
+        if op == "and":
+            return ev(e[1]) & ev(e[2])
+        if op == "or":
+            return ev(e[1]) | ev(e[2])
+        raise ValueError(f"unknown filter op {op!r}")
+
+    keep = np.ones(len(t), dtype=bool)
+    for f in filters:
+        keep &= np.broadcast_to(ev(f), keep.shape)
+    return t[keep]
+
+
 def final_process(table, v2c, plan):
     """The reference's final ops (final_process, sparql.hpp:1424-1551):
     DISTINCT = full-row sort + adjacent equal-on-required-vars removal,
@@ -504,6 +566,12 @@ class GpuExecutor:
         self.engine.last_rows = n
         self._stale = False
         return n
+
+    def execute_filter(self):
+        """The plan's FILTER on the device table (async: outputs <=
+        inputs, the count resolves at the next rows())."""
+        self.engine.execute_filter(sync=False)
+        self._stale = True
 
     def rows(self):
         if self._stale:

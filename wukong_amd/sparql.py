@@ -3,7 +3,9 @@ hot path).
 
 Restates the reference's behavior for the benchmark query class
 (core/parser.hpp + core/SPARQLParser.hpp basic-graph-pattern subset):
-PREFIX declarations, SELECT var list, WHERE { s p o . ... } triples —
+PREFIX declarations, SELECT var list, WHERE { s p o . ... } triples,
+FILTER ( ... ) clauses over =, !=, bound, &&, || and ! (the ID-exact
+subset) —
 plus the planner-plan format of scripts/sparql_query/*/osdi16_plan/*.fmt
 (documented in those files' headers):
 
@@ -96,6 +98,15 @@ def parse(text, vocab, plan_lines=None, distinct=None, limit=None,
         whole = um.group(0)
         union_bodies = re.findall(r"\{([^{}]*)\}", whole)
         body = body[:um.start()] + body[um.end():]
+    # FILTER ( ... ) clauses of the main group, cut out before the triple
+    # split (they may sit between triples, with or without a trailing
+    # '.').  Only the main group may carry one: the engine evaluates the
+    # filter once, over the final table.
+    for grp in [opt_body or ""] + list(union_bodies):
+        if re.search(r"\bFILTER\b", grp, re.I):
+            raise ParseError("FILTER inside an OPTIONAL/UNION group is not "
+                             "supported (DESIGN §7)")
+    body, filter_texts = _cut_filters(body)
     lm = re.search(r"LIMIT\s+(\d+)", text, re.I)
     om = re.search(r"OFFSET\s+(\d+)", text, re.I)
     if limit is None:
@@ -193,10 +204,140 @@ def parse(text, vocab, plan_lines=None, distinct=None, limit=None,
     optional = to_pats(opt_body) if opt_body else []
     unions = [to_pats(b) for b in union_bodies] if union_bodies else []
 
+    # operands resolve through the same term() as the patterns: a
+    # variable used only in a filter still gets an id (the engine then
+    # rejects the plan — no pattern binds it)
+    filters = [_parse_filter(t, term) for t in filter_texts]
+
     req = [vars_[v] for v in sel]
     return Plan(patterns, nvars=len(vars_), required_vars=req,
                 distinct=distinct, limit=limit, offset=offset,
-                optional=optional, unions=unions)
+                optional=optional, unions=unions, filters=filters)
+
+
+def _cut_filters(body):
+    """(body without its FILTER clauses, [expression text of each]) —
+    balanced-parenthesis scan from every FILTER keyword."""
+    out, texts, pos = [], [], 0
+    for m in re.finditer(r"\bFILTER\b", body, re.I):
+        if m.start() < pos:
+            continue
+        i = m.end()
+        while i < len(body) and body[i].isspace():
+            i += 1
+        if i >= len(body) or body[i] != "(":
+            raise ParseError("FILTER must be followed by '('")
+        depth, j = 0, i
+        while j < len(body):
+            if body[j] == "(":
+                depth += 1
+            elif body[j] == ")":
+                depth -= 1
+                if depth == 0:
+                    break
+            j += 1
+        if depth != 0 or j >= len(body):
+            raise ParseError("unbalanced parentheses in FILTER")
+        texts.append(body[i + 1:j])
+        out.append(body[pos:m.start()])
+        out.append(" . ")   # a clause also ends the triple before it
+        pos = j + 1
+    out.append(body[pos:])
+    return "".join(out), texts
+
+
+_FILTER_TOK = re.compile(
+    r"\s*(?:(?P<iri><[^\s<>()]+>)|(?P<op>\|\||&&|!=|<=|>=|=|<|>|!|\(|\)|,)"
+    r"|(?P<lit>\"[^\"]*\"(?:\^\^\S+|@[\w-]+)?)"
+    r"|(?P<word>[^\s()!=<>|&,\"+*/]+)|(?P<bad>\S))")
+
+_NO_STRINGS = ("needs the string server, which is out of scope (DESIGN §7): "
+               "only =, !=, bound, &&, || and ! are evaluated")
+
+
+def _parse_filter(text, term):
+    """One FILTER expression -> nested tuples (the Plan `filters` form).
+
+        or    := and ('||' and)*
+        and   := unary ('&&' unary)*
+        unary := '!' unary | '(' or ')' | bound '(' ?v ')'
+               | operand ('=' | '!=') operand
+    """
+    toks = []
+    for m in _FILTER_TOK.finditer(text):
+        if m.group("bad"):
+            raise ParseError(f"FILTER: {m.group('bad')!r} (arithmetic) "
+                             + _NO_STRINGS)
+        kind = m.lastgroup
+        if kind:
+            toks.append((kind, m.group(kind)))
+    pos = [0]
+
+    def peek():
+        return toks[pos[0]] if pos[0] < len(toks) else (None, None)
+
+    def take(want=None):
+        kind, tok = peek()
+        if kind is None or (want is not None and tok != want):
+            raise ParseError(f"FILTER: expected {want or 'an operand'!r}, "
+                             f"got {tok!r} (unbalanced parentheses?)")
+        pos[0] += 1
+        return kind, tok
+
+    def operand():
+        kind, tok = take()
+        if kind == "op":
+            raise ParseError(f"FILTER: expected an operand, got {tok!r}")
+        return term(tok)
+
+    def p_or():
+        e = p_and()
+        while peek()[1] == "||":
+            take()
+            e = ("or", e, p_and())
+        return e
+
+    def p_and():
+        e = p_unary()
+        while peek()[1] == "&&":
+            take()
+            e = ("and", e, p_unary())
+        return e
+
+    def p_unary():
+        kind, tok = peek()
+        if tok == "!":
+            take()
+            return ("not", p_unary())
+        if tok == "(":
+            take()
+            e = p_or()
+            take(")")
+            return e
+        if kind == "word" and pos[0] + 1 < len(toks) \
+                and toks[pos[0] + 1][1] == "(":
+            if tok.lower() != "bound":
+                raise ParseError(f"FILTER: {tok}() " + _NO_STRINGS)
+            take()
+            take("(")
+            kind, v = take()
+            if kind != "word" or not v.startswith("?"):
+                raise ParseError("FILTER: bound() takes a variable")
+            take(")")
+            return ("bound", term(v))
+        a = operand()
+        kind, tok = take()
+        if tok in ("<", "<=", ">", ">="):
+            raise ParseError(f"FILTER: ordering comparison {tok!r} "
+                             + _NO_STRINGS)
+        if tok not in ("=", "!="):
+            raise ParseError(f"FILTER: expected '=' or '!=', got {tok!r}")
+        return ("eq" if tok == "=" else "ne", a, operand())
+
+    e = p_or()
+    if pos[0] != len(toks):
+        raise ParseError(f"FILTER: trailing {peek()[1]!r}")
+    return e
 
 
 def lubm_entity_vocab(store):
