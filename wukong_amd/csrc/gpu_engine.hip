@@ -2027,9 +2027,13 @@ extern "C" int32_t wk_engine_generate_sub_query(wk_engine_t *e, int32_t ndst,
                        (uint64_t *)e->misc.p, 128);
     const sid_t *cur_tbl = cur_table(e);
     // per-(block,dst) bases live in the prefix scratch: G2*ndst <=
-    // (R/BLOCK+1)*64 entries always fits its (cap_rows+1) u64s
+    // (R/BLOCK+1)*64 entries fit its (cap_rows+1) u64s unless the
+    // capacity is tiny (cap_rows < 84 with ndst = 64), so size it here;
+    // the stream is idle after sync_state and the scratch holds nothing
     const int G2 = (int)std::max<int64_t>(
         1, std::min<int64_t>(1024, (R + BLOCK - 1) / BLOCK));
+    if (e->prefix.ensure((size_t)G2 * ndst * sizeof(unsigned long long)))
+        return WK_ERR_HIP;
     unsigned long long *bh = (unsigned long long *)e->prefix.p;
     if (R) {
         TIME_BEGIN(e);
@@ -2139,8 +2143,12 @@ static int32_t finalize_result(wk_engine *e, const wk_plan_t *plan,
 extern "C" int32_t wk_engine_fetch_result(wk_engine_t *e, const wk_plan_t *plan,
                                           wk_result_t *out) {
     if (!e || !plan || !out) return WK_ERR_STATE;
+    // the device projection writes nrows x nrequired words into the other
+    // table buffer, which holds cap_rows x cap_cols: repeated required
+    // vars can make nrequired exceed cap_cols (nvars 1, nrequired 8), so
+    // those plans project on the host
     const bool simple = !plan->distinct && plan->offset <= 0 && plan->limit < 0 &&
-                        plan->nrequired <= 8;
+                        plan->nrequired <= 8 && plan->nrequired <= e->cap_cols;
     if (!plan->blind && simple && plan->nrequired > 0) {
         // project on DEVICE (sparql.hpp:1510-1536 semantics) and download
         // the projected table directly
