@@ -176,6 +176,27 @@ def edge_graph():
     return triples, meta
 
 
+GATE_W, GATE_RANK, N_GATE = 8, 2, 8
+
+
+def gate_graph():
+    """edge_graph() plus N_GATE subjects (type T_A) with one P_HUB edge
+    each, all owned by rank GATE_RANK of GATE_W partitions.  On that
+    partition (P_HUB, OUT) drops to `edges / keys <= 32` while the full
+    store and the other partitions stay above: the gate of the
+    type-fused CSR path decides differently on one rank."""
+    triples, meta = edge_graph()
+    first = meta["past_max"]
+    first += (GATE_RANK - first) % GATE_W
+    subj = (first + GATE_W * np.arange(N_GATE)).astype(np.uint32)
+    obj = meta["pool"][HUB_DEG - 1]
+    extra = np.array([[s, P_HUB, obj] for s in subj] +
+                     [[s, TYPE, T_A] for s in subj], dtype=np.uint32)
+    meta = dict(meta, gate_s=subj, max_id=int(subj[-1]),
+                past_max=int(subj[-1]) + 1)
+    return np.concatenate([triples, extra]), meta
+
+
 def adjacency(triples):
     """{(vid, pid, dir): sorted uint32 array of neighbours}, straight
     from the triples (type triples have no IN lists: types are index

@@ -178,13 +178,17 @@ def _start_values(meta, lead, big):
 
 
 class StepCase:
-    def __init__(self, cx, op, n, ncols, col, big=False):
+    def __init__(self, cx, op, n, ncols, col, big=False, choose=None):
+        """`choose` maps the start values to the ones to use (the partition
+        tests keep the values one rank owns)."""
         mode, pid, d, lead, pick = OPS[op]
         self.op, self.n, self.ncols, self.col = op, n, ncols, col
         self.mode, self.pid, self.d = mode, pid, d
         self.id = "%s-n%d-c%d" % (op, n, ncols)
         meta = cx.meta
         vals = _start_values(meta, lead, big)
+        if choose is not None:
+            vals = choose(vals)
         r = np.arange(n, dtype=np.int64)
         t = np.empty((n, ncols), dtype=np.uint32)
         for j in range(ncols):
