@@ -18,7 +18,9 @@
  * included below: one translation unit):
  *  wk_kernels_common.h
  *   probe_one/probe_chain, bsearch_u32, tbm_has, csr_entry,
- *   typeof_nodrop_ok — lookup helpers; d_state words and categories
+ *   typeof_nodrop_ok — lookup helpers; d_state words and categories;
+ *   chain_eval (row-major, early exit) and chain_eval_batch (op-major,
+ *   K candidates, no early exit) — the per-row op chain evaluators
  *  wk_kernels_expand.h
  *   k_probe_scan      — fused gen-keys + thread-per-row cluster-hash
  *                       probe + in-kernel prefix scan (2-deep bucket
@@ -31,7 +33,15 @@
  *   k_csr_gather_chain, k_expand_chain[_big] — the same exact pipeline
  *                       with a per-row op chain (chain_t: fn-map
  *                       lookups, bitmap type tests, equality tests of
- *                       the FOLLOWING patterns) as the per-edge predicate
+ *                       the FOLLOWING patterns) as the per-edge predicate;
+ *                       the count pass evaluates it op-major on 2 rows x
+ *                       4 edges per thread (chain_eval_batch, clamped
+ *                       unconditional loads) and leaves a 32-bit pass
+ *                       mask per row, from which the writer emits
+ *   k_row_chain       — a run of >= 2 per-row patterns with no expansion
+ *                       in front as ONE pass over the table: op-major
+ *                       evaluation of 4 rows per thread + ballot
+ *                       compaction at the widened width (Q1's body)
  *   k_scan_local/mid  — chunked exclusive scan with DEVICE-side length
  *                       (replaces the thrust scans, gpu_hash.cu:587-596);
  *                       k_scan_mid also commits the step (S_INROWS
@@ -212,7 +222,7 @@ struct wk_engine {
     // dual result buffer (gpu_mem.hpp:116-124) + scratch, all sized by
     // cap_rows (grow-only; overflow -> re-run)
     devbuf tbl[2];
-    devbuf eoff, cnt, prefix, bsums, misc, ovf;
+    devbuf eoff, cnt, pmask, prefix, bsums, misc, ovf;
     int64_t cap_rows = 0;
     int cap_cols = 0;
 
@@ -302,6 +312,7 @@ struct wk_engine {
 };
 
 static const int BLOCK = 256;
+static_assert(BLOCK == SCAN_T, "kernels declare __launch_bounds__(SCAN_T)");
 static inline const sid_t *cur_table(wk_engine *e);
 static int grid_for(int64_t work) {
     int64_t g = (work + BLOCK - 1) / BLOCK;
@@ -341,6 +352,10 @@ static bool wk_fn_dispatch() {
 // WK_CHAIN=0: run every pattern as a step of its own (no per-row op
 // chain fused into an expansion).  Read per call, like
 // WK_FN_DISPATCH.
+static bool wk_row_chain() {  // WK_ROW_CHAIN=0: expansion tails only
+    const char *v = getenv("WK_ROW_CHAIN");
+    return !(v && v[0] == '0');
+}
 static bool wk_chain() {
     const char *v = getenv("WK_CHAIN");
     return !(v && !atoi(v));
@@ -426,6 +441,8 @@ static int32_t grow_caps(wk_engine *e, int64_t rows, int cols) {
         (void)hipFree(saved);
     }
     if (e->cnt.ensure((size_t)(rows + 1) * 4)) return WK_ERR_HIP;   // u32 degs
+    // u32 per-row pass masks of the chain-fused expansion
+    if (e->pmask.ensure((size_t)(rows + 1) * 4)) return WK_ERR_HIP;
     if (e->eoff.ensure((size_t)(rows + 1) * 8)) return WK_ERR_HIP;
     if (e->prefix.ensure((size_t)(rows + 1) * 8)) return WK_ERR_HIP;
     if (e->ovf.ensure((size_t)(rows + 1) * 4)) return WK_ERR_HIP;
@@ -701,7 +718,8 @@ extern "C" void wk_engine_destroy(wk_engine_t *e) {
     if (!e) return;
     resolve_timing(e);
     for (int i = 0; i < 2; i++) e->tbl[i].release();
-    e->eoff.release(); e->cnt.release(); e->prefix.release();
+    e->eoff.release(); e->cnt.release(); e->pmask.release();
+    e->prefix.release();
     e->bsums.release(); e->misc.release(); e->ovf.release();
     e->oflag[0].release(); e->oflag[1].release();
     for (auto &g : e->graphs)
@@ -1774,13 +1792,15 @@ static int32_t step_k2u_chain(wk_engine *e, const step_ctx &c,
                     dim3(BLOCK), 0, e->stream, c.cur_tbl, c.col, c_pg,
                     e->gs->d_csr_entries[(size_t)c.p * 2 + c.dir], st->fn_base,
                     st->fn_n, e->d_edges, cp.C, e->d_state, e->d_stats,
-                    (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p);
+                    (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p,
+                    (uint32_t *)e->pmask.p);
             });
             TIME_BEGIN(e);
             hipLaunchKernelGGL(
                 k_expand_chain<NC>, dim3(grid_for(e->bound)), dim3(BLOCK), 0,
                 e->stream, c.cur_tbl, e->d_edges, (uint64_t *)e->eoff.p,
-                (uint32_t *)e->cnt.p, (uint64_t *)e->prefix.p,
+                (uint32_t *)e->cnt.p, (uint32_t *)e->pmask.p,
+                (uint64_t *)e->prefix.p,
                 (uint64_t *)e->bsums.p, G, cp.C, cp.out_cols, e->d_state,
                 (uint64_t)e->cap_rows, e->d_stats, (uint32_t *)e->ovf.p,
                 c.out_tbl);
@@ -1795,6 +1815,30 @@ static int32_t step_k2u_chain(wk_engine *e, const step_ctx &c,
     });
     bind_chain_vars(e, cp, nc_in + 1);
     finish_step(e, c.o, cp.out_cols, e->cap_rows, 1 + cp.npat);
+    return WK_OK;
+}
+
+// Stand-alone row pass: a run of >= 2 chain-eligible
+// patterns over the current table (no expansion in front) as one
+// compacting kernel + commit.  Exact: no hint is consulted for the
+// consumed patterns and nothing counts into S_DONE, so inside a capture
+// it replaces the optimistic 1:1 maps and verify-only filters it covers.
+// Output rows <= input rows; e->bound is unchanged.
+static int32_t step_row_chain(wk_engine *e, const step_ctx &c,
+                              const chain_plan &cp) {
+    const int nc_in = e->ncols;
+    TIME_BEGIN(e);
+    with_ncols(nc_in, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        hipLaunchKernelGGL(k_row_chain<NC>, dim3(grid_for(e->bound)),
+                           dim3(BLOCK), 0, e->stream, c.cur_tbl, cp.C,
+                           cp.out_cols, e->d_state, (uint64_t)e->cap_rows,
+                           e->d_stats, c.out_tbl);
+    });
+    TIME_END(e, CAT_FILTER);
+    launch_commit(e);
+    bind_chain_vars(e, cp, nc_in);
+    finish_step(e, 0, cp.out_cols, e->bound, cp.npat);
     return WK_OK;
 }
 
@@ -1888,6 +1932,13 @@ static int32_t exec_pattern(wk_engine *e) {
     const int ostat = e->var_stat(c.o);
     if (!c.seg || c.seg->num_buckets == 0)
         return step_absent_segment(e, c, ostat);
+    // a run of >= 2 per-row patterns from here on: one row pass
+    if (c.key_mode == PK_NORMAL && st->nsrv == 1 && chain_enabled(e) &&
+        wk_row_chain()) {
+        chain_plan cp;
+        collect_chain(e, e->step, e->v2c, e->ncols, cp);
+        if (cp.npat >= 2) return step_row_chain(e, c, cp);
+    }
     if (ostat != 0) return step_filter(e, c, ostat);
     return step_k2u(e, c);
 }

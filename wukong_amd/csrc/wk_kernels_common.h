@@ -94,6 +94,10 @@ enum { CH_FN_APPEND = 0,  // v = fn[row[a]]; 0 drops, else append v
        CH_EQ = 3 };       // row[a] == cval                 (PM_EQ k2c)
 constexpr int CHAIN_MAX = 8;  // ops per chain
 constexpr int ROW_MAX = 8;    // wk_engine_begin_query rejects nvars > 8
+// batched chain evaluation in the fused expansion: edges of one row per
+// round (LUBM takesCourse degrees are 2-4) x rows walked side by side
+constexpr int CHAIN_EK = 4;
+constexpr int CHAIN_RPT = 2;
 
 struct chain_op {
     const fnpage_t *pg;  // FN_*: map pages
@@ -149,6 +153,120 @@ __device__ __forceinline__ bool chain_eval(const chain_t &C,
         }
     }
     return true;
+}
+
+// Column pick for the batched evaluator.  Same contract as row_get, but
+// built from AND/OR masks: a chain of selects between two loaded columns
+// can be rewritten by the optimiser into ONE load at a selected address
+// while the K x ROW_MAX candidate array still lives in memory, which then
+// never becomes registers (observed: 144-400 B of scratch per lane).
+__device__ __forceinline__ sid_t row_pick(const sid_t (&row)[ROW_MAX], int c) {
+    sid_t v = 0;
+#pragma unroll
+    for (int i = 0; i < ROW_MAX; i++) v |= row[i] & (0u - (sid_t)(c == i));
+    return v;
+}
+
+// Op-major evaluation of the chain on K candidate rows at once (DESIGN.md
+// §3 5i): for every op the K loads of one level (bitmap words; map pages;
+// map values) are issued before any of them is consumed, so a thread keeps
+// K independent lookups in flight where chain_eval has one.  Nothing exits
+// early: bit j of the returned mask says whether candidate j is kept (only
+// bits set in `active` can stay set), and a candidate that is inactive or
+// has failed sends its remaining loads to index 0 of the page / value /
+// bitmap array, which exists whenever the op does — the loads are
+// unconditional and the results of dropped candidates are ignored.  An op
+// whose array is null or whose span is empty reads nothing and drops every
+// candidate.  Keep/drop and the appended columns are exactly chain_eval's.
+// APPEND_ONLY: the candidates are known to pass (the count pass said so);
+// only the FN_APPEND lookups are repeated, the filter ops are skipped.
+template <int NC, int K, bool APPEND_ONLY = false>
+__device__ __forceinline__ uint32_t chain_eval_batch(
+    const chain_t &C, sid_t (&rows)[K][ROW_MAX], uint32_t active) {
+    static_assert(K >= 1 && K <= 32, "keep mask is 32 bits");
+    uint32_t keep = active;
+    int nc = NC;
+    // the op loop stays rolled: one op's parameters are read from the
+    // kernel arguments by a wave-uniform index (scalar loads), which keeps
+    // the K-wide body within the register budget
+#pragma unroll 1
+    for (int i = 0; i < C.nops; i++) {
+        const chain_op &o = C.op[i];
+        if (o.kind == CH_TYPE) {
+            if (APPEND_ONLY) continue;
+            const uint64_t *tbm = (const uint64_t *)o.data;
+            if (!tbm || !C.t_n) { keep = 0; continue; }
+            uint64_t ix[K], w[K];
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const uint64_t x = (uint64_t)row_pick(rows[j], o.a) - C.t_base;
+                const bool ok = ((keep >> j) & 1) && x < C.t_n;
+                keep = ok ? keep : keep & ~(1u << j);
+                ix[j] = ok ? x : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++) w[j] = tbm[ix[j] >> 6];
+#pragma unroll
+            for (int j = 0; j < K; j++)
+                keep = ((w[j] >> (ix[j] & 63)) & 1) ? keep : keep & ~(1u << j);
+        } else if (o.kind == CH_EQ) {
+            if (APPEND_ONLY) continue;
+#pragma unroll
+            for (int j = 0; j < K; j++)
+                keep = (row_pick(rows[j], o.a) == o.cval) ? keep
+                                                          : keep & ~(1u << j);
+        } else {
+            if (APPEND_ONLY && o.kind != CH_FN_APPEND) continue;
+            const sid_t *vals = (const sid_t *)o.data;
+            if (!o.pg || !vals || !C.fn_n) {
+                keep = 0;
+                if (o.kind == CH_FN_APPEND) nc++;
+                continue;
+            }
+            uint64_t ix[K], bits[K];
+            uint32_t rk[K];
+            sid_t tv[K];
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const uint64_t x = (uint64_t)row_pick(rows[j], o.a) - C.fn_base;
+                const bool ok = ((keep >> j) & 1) && x < C.fn_n;
+                keep = ok ? keep : keep & ~(1u << j);
+                ix[j] = ok ? x : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++) {  // one 16-B load per page
+                const uint4 q =
+                    *reinterpret_cast<const uint4 *>(&o.pg[ix[j] >> 6]);
+                bits[j] = (uint64_t)q.x | ((uint64_t)q.y << 32);
+                rk[j] = q.z;
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                const uint64_t bit = 1ull << (ix[j] & 63);
+                const bool hit = ((keep >> j) & 1) && (bits[j] & bit);
+                keep = hit ? keep : keep & ~(1u << j);
+                rk[j] = hit ? rk[j] + (uint32_t)__popcll(bits[j] & (bit - 1))
+                            : 0u;
+            }
+#pragma unroll
+            for (int j = 0; j < K; j++) tv[j] = vals[rk[j]];
+            if (o.kind == CH_FN_EQ) {
+#pragma unroll
+                for (int j = 0; j < K; j++)
+                    keep = (tv[j] && tv[j] == row_pick(rows[j], o.b))
+                               ? keep
+                               : keep & ~(1u << j);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; j++) {
+                    keep = tv[j] ? keep : keep & ~(1u << j);
+                    row_set(rows[j], nc, tv[j]);
+                }
+                nc++;
+            }
+        }
+    }
+    return keep;
 }
 
 // one cluster-hash lookup: walk the bucket chain, 7 slot compares per

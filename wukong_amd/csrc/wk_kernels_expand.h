@@ -284,8 +284,13 @@ __global__ void k_expand_tf_big(const sid_t *__restrict__ tbl, int ncols,
 // value, the chain tests it (and may append further columns), d_cnt gets
 // the number of PASSING edges.  Siblings of the typeof-only kernels
 // above, which stay as they are (both of their paths are measured).
+// The count pass evaluates the chain op-major (chain_eval_batch) and
+// leaves a 32-bit pass mask per row (bit k = edge k passes) in d_pmask,
+// so the writer of a <= 32-edge row takes the passing edges from the
+// mask and repeats only the chain's FN_APPEND lookups.
 template <int NC>
-__global__ void k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
+__global__ void __launch_bounds__(SCAN_T)
+k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
                                    const fnpage_t *__restrict__ pg,
                                    const uint64_t *__restrict__ entries,
                                    uint64_t base, uint64_t n,
@@ -294,39 +299,98 @@ __global__ void k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
                                    const uint64_t *__restrict__ d_state,
                                    uint64_t *__restrict__ d_stats,
                                    uint64_t *__restrict__ d_eoff,
-                                   uint32_t *__restrict__ d_cnt)
+                                   uint32_t *__restrict__ d_cnt,
+                                   uint32_t *__restrict__ d_pmask)
 {
     static_assert(NC < ROW_MAX, "the edge value needs a column");
+    static_assert(32 % CHAIN_EK == 0, "pass-mask groups must tile 32 bits");
+    constexpr int RPT = CHAIN_RPT, EK = CHAIN_EK, K = RPT * EK;
     const int64_t nrows = (int64_t)d_state[S_NROWS];
-    count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 * NC + 16 + 8 + 12));
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
-        sid_t row[ROW_MAX];
+    count_bytes(d_stats, CAT_PROBE,
+                (uint64_t)nrows * (4 * NC + 16 + 8 + 12 + 4));
+    // a thread takes RPT rows H apart and walks their edge lists side by
+    // side, EK edges of each per round: K candidates per chain_eval_batch
+    // call.  H is the grid stride T, or ceil(nrows / RPT) for a table of
+    // fewer than RPT * T rows (one round, threads below H), so that small
+    // tables pair rows too.  A row past the end or out of edges is
+    // inactive (its loads go to edges[0], which always exists).
+    const int64_t T = (int64_t)gridDim.x * blockDim.x;
+    const int64_t H = min(T, (nrows + RPT - 1) / RPT);
+    const int64_t lim = H < T ? H : nrows;
+    for (int64_t r0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         r0 < lim; r0 += T * RPT) {
+        sid_t in[RPT][NC];
+        uint64_t e[RPT];
+        uint32_t len[RPT], keep[RPT], pmask[RPT];
 #pragma unroll
-        for (int c = 0; c < ROW_MAX; c++) row[c] = 0;
+        for (int q = 0; q < RPT; q++) {
+            const int64_t r = r0 + q * H;
+            const int64_t rr = r < nrows ? r : r0;
 #pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-        const uint64_t e =
-            csr_entry(pg, entries, base, n, row_get(row, col));
-        const uint64_t off = csr_off(e);
-        const uint32_t len = csr_len(e);
-        uint32_t keep = 0;
-        for (uint32_t k = 0; k < len; k++) {
-            row[NC] = edges[off + k];
-            keep += chain_eval<NC + 1>(C, row) ? 1u : 0u;
+            for (int c = 0; c < NC; c++) in[q][c] = tbl[rr * NC + c];
         }
-        d_eoff[r] = e;  // {off:40|len:24} for the writer's re-walk
-        d_cnt[r] = keep;
+        uint32_t maxlen = 0;
+#pragma unroll
+        for (int q = 0; q < RPT; q++) {
+            sid_t key = in[q][0];
+#pragma unroll
+            for (int c = 1; c < NC; c++) key = (col == c) ? in[q][c] : key;
+            e[q] = csr_entry(pg, entries, base, n, key);
+            len[q] = (r0 + q * H < nrows) ? csr_len(e[q]) : 0u;
+            keep[q] = 0;
+            pmask[q] = 0;
+            maxlen = max(maxlen, len[q]);
+        }
+        for (uint32_t k0 = 0; k0 < maxlen; k0 += EK) {
+            sid_t cand[K][ROW_MAX];
+            uint32_t active = 0;
+#pragma unroll
+            for (int q = 0; q < RPT; q++) {
+                const uint64_t off = csr_off(e[q]);
+#pragma unroll
+                for (int j = 0; j < EK; j++) {
+                    const bool on = k0 + j < len[q];
+                    active |= on ? 1u << (q * EK + j) : 0u;
+#pragma unroll
+                    for (int c = 0; c < ROW_MAX; c++) cand[q * EK + j][c] = 0;
+#pragma unroll
+                    for (int c = 0; c < NC; c++)
+                        cand[q * EK + j][c] = in[q][c];
+                    cand[q * EK + j][NC] = edges[on ? off + k0 + j : 0];
+                }
+            }
+            const uint32_t m = chain_eval_batch<NC + 1, K>(C, cand, active);
+#pragma unroll
+            for (int q = 0; q < RPT; q++) {
+                const uint32_t mq = (m >> (q * EK)) & ((1u << EK) - 1);
+                keep[q] += (uint32_t)__popc(mq);
+                // bit k of the pass mask = edge k passes (rows of <= 32
+                // edges; the writer sends longer rows to the wave pass)
+                pmask[q] |= k0 < 32 ? mq << k0 : 0u;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < RPT; q++) {
+            const int64_t r = r0 + q * H;
+            if (r < nrows) {
+                d_eoff[r] = e[q];  // {off:40|len:24} for the writer
+                d_cnt[r] = keep[q];
+                d_pmask[r] = pmask[q];
+            }
+        }
     }
 }
 
-// writer: re-walk, re-evaluate, emit the passing (widened) rows at the
-// exact scanned positions; rows with > 32 edges go to the wave pass
+// writer: emit the passing (widened) rows at the exact scanned positions,
+// taking the passing edges from the count pass's mask; rows with > 32
+// edges go to the wave pass, which re-evaluates the chain
 template <int NC>
-__global__ void k_expand_chain(const sid_t *__restrict__ tbl,
+__global__ void __launch_bounds__(SCAN_T)
+k_expand_chain(const sid_t *__restrict__ tbl,
                                const sid_t *__restrict__ edges,
                                const uint64_t *__restrict__ d_eoff,
                                const uint32_t *__restrict__ d_cnt,
+                               const uint32_t *__restrict__ d_pmask,
                                const uint64_t *__restrict__ d_pre,
                                const uint64_t *__restrict__ bsums, int G,
                                chain_t C, int oc,
@@ -336,6 +400,7 @@ __global__ void k_expand_chain(const sid_t *__restrict__ tbl,
                                sid_t *__restrict__ out)
 {
     static_assert(NC < ROW_MAX, "the edge value needs a column");
+    constexpr int EK = CHAIN_EK;
     const int64_t nrows = (int64_t)d_state[S_INROWS];
     const int64_t chunk = (nrows + G - 1) / G;
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows;
@@ -353,30 +418,49 @@ __global__ void k_expand_chain(const sid_t *__restrict__ tbl,
             ovf[i] = (uint32_t)r;
             continue;
         }
-        sid_t row[ROW_MAX];
+        sid_t in[NC];
 #pragma unroll
-        for (int c = 0; c < ROW_MAX; c++) row[c] = 0;
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
+        for (int c = 0; c < NC; c++) in[c] = tbl[r * NC + c];
         sid_t *dst = out + (int64_t)basep * oc;
         uint32_t w = 0;
-        for (uint32_t k = 0; k < len && w < keep; k++) {
-            row[NC] = edges[off + k];
-            if (!chain_eval<NC + 1>(C, row)) continue;
-            if (basep + w >= cap) break;
+        // the passing edges, lowest first, EK at a time: their values are
+        // loaded together, and so are the FN_APPEND lookups of a chain
+        // that widens the row (off is valid: keep > 0 means len > 0)
+        for (uint32_t m = d_pmask[r]; m;) {
+            sid_t cand[EK][ROW_MAX];
+            uint32_t act = 0;
 #pragma unroll
-            for (int c = 0; c < ROW_MAX; c++)
-                if (c < oc) dst[c] = row[c];
-            dst += oc;
-            w++;
+            for (int j = 0; j < EK; j++) {
+                const bool on = m != 0;
+                const uint32_t p = on ? (uint32_t)__ffs((int)m) - 1u : 0u;
+                m &= m - 1;
+                act |= on ? 1u << j : 0u;
+#pragma unroll
+                for (int c = 0; c < ROW_MAX; c++) cand[j][c] = 0;
+#pragma unroll
+                for (int c = 0; c < NC; c++) cand[j][c] = in[c];
+                cand[j][NC] = edges[off + p];
+            }
+            if (oc > NC + 1)
+                act = chain_eval_batch<NC + 1, EK, true>(C, cand, act);
+#pragma unroll
+            for (int j = 0; j < EK; j++) {
+                if (((act >> j) & 1) && basep + w < cap) {
+#pragma unroll
+                    for (int c = 0; c < ROW_MAX; c++)
+                        if (c < oc) dst[c] = cand[j][c];
+                    dst += oc;
+                    w++;
+                }
+            }
         }
     }
-    // written rows + per-input-row scan words (the walk itself is counted
-    // by the gather)
+    // written rows + per-input-row scan words and pass mask (the walk
+    // itself is counted by the gather)
     if (blockIdx.x == 0 && threadIdx.x == 0)
         atomicAdd((unsigned long long *)&d_stats[CAT_EXPAND],
                   (unsigned long long)(d_state[S_NROWS] * (4 * oc) +
-                                       (uint64_t)nrows * 20));
+                                       (uint64_t)nrows * 24));
 }
 
 template <int NC>
@@ -430,6 +514,77 @@ __global__ void k_expand_chain_big(const sid_t *__restrict__ tbl,
                 }
             }
             wbase += (uint64_t)__popcll(mask);
+        }
+    }
+}
+
+// Stand-alone row pass: a run of >= 2 per-row patterns
+// that does not follow a CSR expansion, as ONE kernel over the table
+// (possibly a zero-copy view): each thread evaluates the chain op-major
+// on the 4 rows of its tile slots (chain_eval_batch), survivors are
+// compacted at the widened width with k_filter_tpr's ballot ranks (one
+// LDS atomic per wave, one S_TOTAL atomic per 1024-row tile); k_commit
+// follows.  Exact; nothing counts into S_DONE.
+template <int NC>
+__global__ void __launch_bounds__(SCAN_T)
+k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
+            uint64_t *__restrict__ d_state, uint64_t cap,
+            uint64_t *__restrict__ d_stats, sid_t *__restrict__ out)
+{
+    constexpr int K = 4;
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * (4 * NC + 4 * oc));
+    __shared__ unsigned long long s_base;
+    __shared__ unsigned int s_cnt;
+    __shared__ unsigned int s_wbase[SCAN_T / 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const int64_t tile = (int64_t)SCAN_T * K;
+    const int64_t stride = (int64_t)gridDim.x * tile;
+    for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows;
+         base += stride) {
+        sid_t rows[K][ROW_MAX];
+        uint32_t active = 0;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const int64_t r = base + k * SCAN_T + threadIdx.x;
+            const bool in = r < nrows;
+            const int64_t rr = in ? r : base;  // base < nrows: a valid row
+            active |= in ? 1u << k : 0u;
+#pragma unroll
+            for (int c = 0; c < ROW_MAX; c++) rows[k][c] = 0;
+#pragma unroll
+            for (int c = 0; c < NC; c++) rows[k][c] = tbl[rr * NC + c];
+        }
+        const uint32_t keep = chain_eval_batch<NC, K>(C, rows, active);
+        if (threadIdx.x == 0) s_cnt = 0;
+        __syncthreads();
+        uint64_t mask[K];
+        uint32_t wtot = 0;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            mask[k] = __ballot((keep >> k) & 1);
+            wtot += (uint32_t)__popcll(mask[k]);
+        }
+        if (lane == 0) s_wbase[wid] = atomicAdd(&s_cnt, wtot);
+        __syncthreads();
+        if (threadIdx.x == 0)
+            s_base = s_cnt ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
+                                       (unsigned long long)s_cnt)
+                           : 0;
+        __syncthreads();
+        uint64_t wpos = s_base + s_wbase[wid];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const uint64_t pos =
+                wpos + (uint32_t)__popcll(mask[k] & ((1ull << lane) - 1));
+            if (((keep >> k) & 1) && pos < cap) {  // past cap: k_commit flags
+                sid_t *dst = out + (int64_t)pos * oc;
+#pragma unroll
+                for (int c = 0; c < ROW_MAX; c++)
+                    if (c < oc) dst[c] = rows[k][c];
+            }
+            wpos += (uint32_t)__popcll(mask[k]);
         }
     }
 }
