@@ -212,7 +212,14 @@ int32_t wk_engine_light_batch_wait(wk_engine_t *, uint64_t *counts,
  * launch chain once (after a warm pass settles capacities); run
  * replays it in ONE hipGraphLaunch and returns the blind row count.
  * WK_ERR_CAP from run = capacity overflow (data changed since build):
- * fall back to wk_engine_submit. */
+ * fall back to wk_engine_submit.
+ * A plan with distinct / limit >= 0 / offset > 0 is accepted when the
+ * device final ops are on (WK_DEV_FINAL, default 1) and the plan is
+ * non-blind with 1..8 required vars: its chain ends with the device
+ * final pass.  run still returns the blind (pre-final) count;
+ * wk_engine_final_count reads the post-final one, and
+ * wk_engine_fetch_result of the same plan downloads the table the replay
+ * already finalized.  Otherwise such a plan is WK_ERR_PLAN (-3). */
 int32_t wk_engine_graph_build(wk_engine_t *, const wk_plan_t *,
                               int32_t *graph_id);
 int32_t wk_engine_graph_run(wk_engine_t *, int32_t graph_id,
@@ -308,8 +315,20 @@ int32_t wk_engine_execute_one_pattern_remote(wk_engine_t *, int64_t *nrows_out);
 int32_t wk_engine_generate_sub_query(wk_engine_t *, int32_t ndst,
                                      wk_sid_t *dev_out, int64_t cap_rows,
                                      int64_t *rows_per_dst);
-/* Finish: run remaining host-side final ops and download. */
+/* Finish: run the final ops (DISTINCT, OFFSET, LIMIT, projection) and
+ * download.  Non-blind plans with final ops run them on the device
+ * (WK_DEV_FINAL=0, or more than 8 required vars: on the host, after a
+ * full-table download) and download only the final rows; the current
+ * table is left as it was (wk_engine_fetch_raw still returns it). */
 int32_t wk_engine_fetch_result(wk_engine_t *, const wk_plan_t *, wk_result_t *out);
+/* Post-final-ops row count of the last non-blind fetch_result or of the
+ * last replay of a final-op graph, without a download.  WK_ERR_STATE
+ * (-4) when no final pass has run on the current table (begin_query,
+ * load_rbuf*, a step or another replay drop it). */
+int32_t wk_engine_final_count(wk_engine_t *, int64_t *n);
+/* Digit passes of the last device DISTINCT: live = passes that ran,
+ * total = 4 per column (constant digits are skipped on the device). */
+int32_t wk_engine_final_passes(wk_engine_t *, int32_t *live, int32_t *total);
 /* Download the CURRENT binding table without final ops (tests/driver). */
 int32_t wk_engine_fetch_raw(wk_engine_t *, wk_result_t *out);
 

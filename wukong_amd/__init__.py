@@ -190,6 +190,10 @@ _eng_pattern_step = _sig("wk_engine_pattern_step", c_i32, [c_vp])
 _eng_col_num = _sig("wk_engine_col_num", c_i32, [c_vp])
 _eng_subq = _sig("wk_engine_generate_sub_query", c_i32, [c_vp, c_i32, c_vp, c_i64, ctypes.POINTER(c_i64)])
 _eng_fetch = _sig("wk_engine_fetch_result", c_i32, [c_vp, ctypes.POINTER(WkPlan), ctypes.POINTER(WkResult)])
+_eng_final_count = _sig("wk_engine_final_count", c_i32,
+                        [c_vp, ctypes.POINTER(c_i64)])
+_eng_final_passes = _sig("wk_engine_final_passes", c_i32,
+                         [c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)])
 _eng_fetch_raw = _sig("wk_engine_fetch_raw", c_i32, [c_vp, ctypes.POINTER(WkResult)])
 _res_free = _sig("wk_result_free", None, [ctypes.POINTER(WkResult)])
 _kstats = _sig("wk_engine_kernel_stats", c_i32, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64)])
@@ -477,7 +481,10 @@ class Engine:
 
     def graph_build(self, plan):
         """Capture the plan's whole launch chain as a hipGraph (one
-        warm pass first); returns a graph id for graph_run."""
+        warm pass first); returns a graph id for graph_run.  A plan with
+        distinct/limit/offset ends its chain with the device final pass
+        (refused with WK_DEV_FINAL=0, for blind plans and for more than 8
+        required vars: rc=-3)."""
         cplan = plan.to_c()
         gid = c_i32()
         rc = _eng_graph_build(self._h, ctypes.byref(cplan), ctypes.byref(gid))
@@ -486,9 +493,11 @@ class Engine:
         return int(gid.value)
 
     def graph_run(self, gid):
-        """Replay a captured plan (ONE hipGraphLaunch); blind row count.
-        Raises OverflowError on capacity overflow — fall back to
-        submit()."""
+        """Replay a captured plan (ONE hipGraphLaunch); blind row count
+        (pre-DISTINCT/OFFSET/LIMIT, also for a final-op plan: its
+        post-final count is final_count(), its finalized table
+        fetch_result(plan)).  Raises OverflowError on capacity overflow —
+        fall back to submit()."""
         n = c_i64()
         rc = _eng_graph_run(self._h, gid, ctypes.byref(n))
         if rc == -5:
@@ -724,7 +733,33 @@ class Engine:
         _res_free(ctypes.byref(res))
         return n
 
+    def final_count(self):
+        """Row count after DISTINCT/OFFSET/LIMIT of the last non-blind
+        fetch_result / run_query, or of the last graph_run of a final-op
+        plan — no download.  RuntimeError when no final pass has run on
+        the current table (begin_query, load_rbuf, a step or another
+        replay drop it)."""
+        n = c_i64()
+        rc = _eng_final_count(self._h, ctypes.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"final_count rc={rc}")
+        return int(n.value)
+
+    def final_passes(self):
+        """(live, total) digit passes of the last device DISTINCT."""
+        a, b = c_i32(), c_i32()
+        rc = _eng_final_passes(self._h, ctypes.byref(a), ctypes.byref(b))
+        if rc != 0:
+            raise RuntimeError(f"final_passes rc={rc}")
+        return int(a.value), int(b.value)
+
     def fetch_result(self, plan=None):
+        """Final ops + download of the current query.  DISTINCT, OFFSET,
+        LIMIT and the projection run on the device (WK_DEV_FINAL=0: on
+        the host); the current table stays what it was, so fetch_raw()
+        still returns it.  After graph_run(gid) of a final-op plan,
+        fetch_result(plan) of that plan downloads the table the replay
+        finalized, without recomputing it."""
         cplan = self._cplan if plan is None else plan.to_c()
         res = WkResult()
         rc = _eng_fetch(self._h, ctypes.byref(cplan), ctypes.byref(res))

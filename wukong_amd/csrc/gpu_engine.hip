@@ -83,6 +83,14 @@
  *   k_plan_batch      — LDS plan interpreter: whole multi-pattern
  *                       const-start templates, binding table in LDS
  *   k_peer_step       — xGMI peer-probe small-table step
+ *  wk_kernels_final.h
+ *   k_fin_live/hist/scan/scatter — DISTINCT as a stable LSD radix sort of
+ *                       a row-index permutation (8-bit digits, constant
+ *                       digits skipped on the device); k_fin_flag/emit —
+ *                       adjacent dedup + OFFSET/LIMIT window + projection
+ *                       in one compaction; k_fin_window — the window
+ *                       alone (replaces the host final_process,
+ *                       sparql.hpp:1424-1551; captured into graphs)
  *  host side (this file)
  *   zero-copy i2u/c2u — the 1-col start table IS the stored edge list
  *                       (read-only view, no copy kernel)
@@ -140,6 +148,7 @@ enum {
 #include "wk_kernels_expand.h"
 #include "wk_kernels_filter.h"
 #include "wk_kernels_batch.h"
+#include "wk_kernels_final.h"
 
 // ---------------------------------------------------------------------
 // engine
@@ -223,11 +232,13 @@ struct wk_engine {
     // cap_rows (grow-only; overflow -> re-run)
     devbuf tbl[2];
     devbuf eoff, cnt, pmask, prefix, bsums, misc, ovf;
+    devbuf fhist;  // final ops: block x digit histograms (by cap_rows)
     int64_t cap_rows = 0;
     int cap_cols = 0;
 
     uint64_t *d_state = nullptr;  // S_WORDS words
     uint64_t *d_stats = nullptr;  // CAT_COUNT words (algorithmic bytes)
+    uint64_t *d_fin = nullptr;    // F_WORDS words (final-ops state)
     uint64_t *h_pin = nullptr;    // pinned: state + stats snapshot
     void *h_stage = nullptr;      // pinned staging for result downloads
     size_t h_stage_cap = 0;
@@ -254,6 +265,25 @@ struct wk_engine {
     // replaying a 25-MB k_copy_list per query.  Cleared on every table
     // flip/load; materialised before any in-place writer (OPT groups).
     const sid_t *tbl_view = nullptr;
+
+    // final ops of the CURRENT table.  fin_count: the
+    // post-final row count of the last non-blind fetch or final-op replay
+    // (-1 = none); fin_table: the finalized, projected table for fin_sig
+    // sits in tbl[cur ^ 1].  Both are dropped by whatever changes the
+    // current table (fin_invalidate).
+    struct fin_sig_t {
+        int32_t distinct = 0, nrequired = 0;
+        int64_t limit = -1, offset = 0;
+        int32_t req[8] = {0};
+        bool operator==(const fin_sig_t &o) const {
+            return distinct == o.distinct && nrequired == o.nrequired &&
+                   limit == o.limit && offset == o.offset &&
+                   !memcmp(req, o.req, sizeof(req));
+        }
+    };
+    int64_t fin_count = -1;
+    bool fin_table = false;
+    fin_sig_t fin_sig;
 
     // OPTIONAL group execution state (wk_engine_run_query only)
     devbuf oflag[2];          // per-row matched flags (u8), ping-pong
@@ -290,6 +320,8 @@ struct wk_engine {
         int64_t bound = 0;
         bool light = false;
         const sid_t *view = nullptr;  // final table is a zero-copy view
+        bool fin = false;  // the chain ends with the final pass (fin_sig)
+        fin_sig_t fin_sig;
     };
     std::vector<wk_graph> graphs;
     int capturing = 0;
@@ -333,6 +365,15 @@ static int32_t materialize_view(wk_engine *e) {
         return WK_ERR_HIP;
     e->tbl_view = nullptr;
     return WK_OK;
+}
+static inline void fin_invalidate(wk_engine *e) {
+    e->fin_count = -1;
+    e->fin_table = false;
+}
+// blocks of the final-ops histogram/scatter grid: fixed by the capacity
+static int fin_grid(int64_t cap_rows) {
+    int64_t g = (cap_rows + BLOCK - 1) / BLOCK;
+    return (int)(g < 1 ? 1 : (g > FIN_MAXB ? FIN_MAXB : g));
 }
 static int scan_grid(int64_t bound) {
     int64_t g = (bound + SCAN_T) / SCAN_T + 1;
@@ -427,6 +468,7 @@ static int32_t grow_caps(wk_engine *e, int64_t rows, int cols) {
     rows = std::max(rows, e->cap_rows);
     // one sync before freeing buffers that in-flight kernels may use
     HIP_CHECK(stream_sync(e->stream));
+    fin_invalidate(e);  // the finalized table lives in the old buffers
     size_t keep = (size_t)std::max<int64_t>(e->nrows, 0) * std::max(e->ncols, 0) * 4;
     keep = std::min(keep, e->tbl[e->cur].cap);
     void *saved = nullptr;
@@ -447,6 +489,7 @@ static int32_t grow_caps(wk_engine *e, int64_t rows, int cols) {
     if (e->prefix.ensure((size_t)(rows + 1) * 8)) return WK_ERR_HIP;
     if (e->ovf.ensure((size_t)(rows + 1) * 4)) return WK_ERR_HIP;
     if (e->bsums.ensure(2056 * 8)) return WK_ERR_HIP;
+    if (e->fhist.ensure((size_t)fin_grid(rows) * 256 * 4)) return WK_ERR_HIP;
     e->cap_rows = rows;
     e->cap_cols = cols;
     return WK_OK;
@@ -696,7 +739,9 @@ extern "C" wk_engine_t *wk_engine_create_on(wk_gpu_store_t *g) {
         return nullptr;
     }
     e->d_stats = e->d_state + S_WORDS;
-    if (hipMemset(e->d_state, 0, (S_WORDS + CAT_COUNT + 2) * 8) != hipSuccess) {
+    if (hipMalloc(&e->d_fin, F_WORDS * 8) != hipSuccess ||
+        hipMemset(e->d_fin, 0, F_WORDS * 8) != hipSuccess ||
+        hipMemset(e->d_state, 0, (S_WORDS + CAT_COUNT + 2) * 8) != hipSuccess) {
         wk_engine_destroy(e);
         return nullptr;
     }
@@ -721,12 +766,14 @@ extern "C" void wk_engine_destroy(wk_engine_t *e) {
     e->eoff.release(); e->cnt.release(); e->pmask.release();
     e->prefix.release();
     e->bsums.release(); e->misc.release(); e->ovf.release();
+    e->fhist.release();
     e->oflag[0].release(); e->oflag[1].release();
     for (auto &g : e->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     e->lbd.release(); e->lbcnt.release();
     if (e->h_lb) (void)hipHostFree(e->h_lb);
     if (e->d_state) (void)hipFree(e->d_state);
+    if (e->d_fin) (void)hipFree(e->d_fin);
     if (e->h_pin) (void)hipHostFree(e->h_pin);
     if (e->h_stage) (void)hipHostFree(e->h_stage);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -858,6 +905,7 @@ extern "C" int32_t wk_engine_begin_query(wk_engine_t *e, const wk_plan_t *plan) 
     e->tbl_view = nullptr;
     e->bound = 0;
     e->light = false;
+    fin_invalidate(e);
     int32_t rc = grow_caps(e, e->cap_rows, plan->nvars);
     if (rc) return rc;
     // reset nrows + overflow flags on device: deferred to the query's
@@ -907,6 +955,7 @@ static int32_t begin_light(wk_engine *e, const wk_plan_t *plan) {
     e->tbl_view = nullptr;
     e->bound = 0;
     e->light = true;
+    fin_invalidate(e);
     e->zero_pending = false;  // k_light2 writes S_NROWS/S_ERR itself
     return grow_caps(e, e->cap_rows, plan->nvars);
 }
@@ -915,6 +964,7 @@ static int32_t load_common(wk_engine *e, int64_t nrows, int32_t ncols,
                            const int32_t *v2c_map, int32_t pattern_step) {
     e->cur = 0;
     e->tbl_view = nullptr;
+    fin_invalidate(e);
     e->nrows = nrows;
     e->bound = nrows;
     e->ncols = ncols;
@@ -1156,6 +1206,7 @@ static void bind_chain_vars(wk_engine *e, const chain_plan &cp, int first_col) {
 static void finish_step_in_place(wk_engine *e, ssid_t new_var, int out_cols,
                                  int64_t bound, int consumed) {
     if (new_var < 0) e->v2c[-(new_var + 1)] = e->ncols;
+    fin_invalidate(e);
     e->ncols = out_cols;
     e->bound = bound;
     e->step += consumed;
@@ -2150,8 +2201,12 @@ static int32_t finalize_result(wk_engine *e, const wk_plan_t *plan,
             return false;
         });
         std::vector<int> rcols;
-        for (int i = 0; i < plan->nrequired; i++)
-            rcols.push_back(e->var2col(plan->required_vars[i]));
+        // a required var with no column compares equal on every row
+        // (indexing with its -1 would read the neighbouring row)
+        for (int i = 0; i < plan->nrequired; i++) {
+            int c = e->var2col(plan->required_vars[i]);
+            if (c >= 0) rcols.push_back(c);
+        }
         std::vector<sid_t> kept;
         kept.reserve(tbl.size());
         auto eq_req = [&](int64_t a, int64_t b) {
@@ -2188,12 +2243,162 @@ static int32_t finalize_result(wk_engine *e, const wk_plan_t *plan,
     out->row_num = Rn;
     out->table = res;
     out->status_code = 0;
+    e->fin_count = Rn;
+    return WK_OK;
+}
+
+// ---- device final ops -------------------------------
+// WK_DEV_FINAL=0: DISTINCT/OFFSET/LIMIT on the host (finalize_result) and
+// no final-op plans in graphs.  Read per call, like WK_CHAIN.
+static bool wk_dev_final() {
+    const char *v = getenv("WK_DEV_FINAL");
+    return !(v && !atoi(v));
+}
+// WK_FINAL_HOST_ROWS (default 8192, read per call): a non-captured fetch
+// of fewer rows keeps the host final ops — below that the ~30-launch
+// device chain costs more than the host sort.  0 = always
+// the device.  Captured graphs always end with the device pass.
+static int64_t wk_final_host_rows() {
+    const char *v = getenv("WK_FINAL_HOST_ROWS");
+    return v ? atoll(v) : 8192;
+}
+static bool plan_has_final(const wk_plan_t *plan) {
+    return plan->distinct || plan->limit >= 0 || plan->offset > 0;
+}
+// The device pass writes final_rows x nrequired words into the other
+// table buffer (cap_rows x cap_cols) and indexes rows with u32.
+static bool dev_final_ok(const wk_engine *e, const wk_plan_t *plan) {
+    return plan->nrequired > 0 && plan->nrequired <= 8 &&
+           plan->nrequired <= e->cap_cols && e->ncols >= 1 && e->ncols <= 8 &&
+           e->cap_rows < ((int64_t)1 << 32);
+}
+static wk_engine::fin_sig_t fin_sig_of(const wk_plan_t *plan) {
+    wk_engine::fin_sig_t s;
+    s.distinct = plan->distinct ? 1 : 0;
+    s.nrequired = plan->nrequired;
+    s.limit = plan->limit >= 0 ? plan->limit : -1;
+    s.offset = plan->offset > 0 ? plan->offset : 0;
+    for (int j = 0; j < plan->nrequired && j < 8; j++)
+        s.req[j] = plan->required_vars[j];
+    return s;
+}
+
+// Enqueue the final pass over the current table (no sync, capturable: all
+// scratch is sized by cap_rows in grow_caps, row counts come from
+// d_state).  The finalized, projected table goes to tbl[cur ^ 1]; the
+// current table — possibly a store view — is only read, and stays current.
+static void launch_final(wk_engine *e, const wk_plan_t *plan) {
+    flush_begin(e);
+    fin_tbl T{cur_table(e), e->ncols, e->d_state, (uint64_t)e->cap_rows,
+              e->d_fin, {(uint32_t *)e->cnt.p, (uint32_t *)e->pmask.p}};
+    fin_emit E{};
+    for (int j = 0; j < 8; j++)
+        E.cols.c[j] = j < plan->nrequired ? e->var2col(plan->required_vars[j]) : -1;
+    E.rc = plan->nrequired;
+    E.offset = plan->offset > 0 ? (uint64_t)plan->offset : 0;
+    E.limit = plan->limit >= 0 ? (uint64_t)plan->limit : ~(uint64_t)0;
+    E.out = (sid_t *)e->tbl[e->cur ^ 1].p;
+    TIME_BEGIN(e);
+    if (plan->distinct) {
+        const int G = fin_grid(e->cap_rows);
+        uint32_t *hist = (uint32_t *)e->fhist.p;
+        hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, e->stream,
+                           e->d_fin, F_WORDS);
+        hipLaunchKernelGGL(k_fin_live, dim3(grid_for(e->cap_rows)), dim3(BLOCK),
+                           0, e->stream, T);
+        for (int p = 0; p < 4 * e->ncols; p++) {
+            hipLaunchKernelGGL(k_fin_hist, dim3(G), dim3(BLOCK), 0, e->stream,
+                               T, p, hist);
+            hipLaunchKernelGGL(k_fin_scan, dim3(1), dim3(FIN_SCAN_T), 0,
+                               e->stream, T, p, hist, G);
+            hipLaunchKernelGGL(k_fin_scatter, dim3(G), dim3(BLOCK), 0,
+                               e->stream, T, p, hist);
+        }
+        // the block x digit matrix is done with: its head holds the
+        // per-block kept counts
+        hipLaunchKernelGGL(k_fin_flag, dim3(G), dim3(BLOCK), 0, e->stream, T, E,
+                           (uint32_t *)e->ovf.p, hist);
+        hipLaunchKernelGGL(k_fin_emit, dim3(G), dim3(BLOCK), 0, e->stream, T, E,
+                           (const uint32_t *)e->ovf.p, hist);
+    } else {
+        hipLaunchKernelGGL(k_fin_window, dim3(grid_for(e->cap_rows)),
+                           dim3(BLOCK), 0, e->stream, T, E);
+    }
+    hipLaunchKernelGGL(k_fin_publish, dim3(1), dim3(1), 0, e->stream, e->d_fin,
+                       e->h_pin);
+    TIME_END(e, CAT_OTHER);
+}
+
+extern "C" int32_t wk_engine_final_count(wk_engine_t *e, int64_t *n) {
+    if (!e || !n || e->fin_count < 0) return WK_ERR_STATE;
+    *n = e->fin_count;
+    return WK_OK;
+}
+
+// Digit passes of the last device DISTINCT: how many ran, out of how many
+// (4 per column); 0/0 when the last final pass sorted nothing.
+extern "C" int32_t wk_engine_final_passes(wk_engine_t *e, int32_t *live,
+                                          int32_t *total) {
+    if (!e || !live || !total || !e->fin_table) return WK_ERR_STATE;
+    *live = *total = 0;
+    if (!e->fin_sig.distinct) return WK_OK;
+    for (int c = 0; c < e->ncols && c < 8; c++)
+        for (int k = 0; k < 4; k++)
+            *live += ((e->h_pin[HP_FIN_LIVE + c] >> (8 * k)) & 0xFF) != 0;
+    *total = 4 * e->ncols;
     return WK_OK;
 }
 
 extern "C" int32_t wk_engine_fetch_result(wk_engine_t *e, const wk_plan_t *plan,
                                           wk_result_t *out) {
     if (!e || !plan || !out) return WK_ERR_STATE;
+    bool synced = false;  // the row-count cutoff below already synced
+    if (!plan->blind && plan_has_final(plan) && wk_dev_final() &&
+        dev_final_ok(e, plan)) {
+        // final ops on DEVICE; after a replay of a graph that ends with
+        // this very final pass the table is already there
+        const wk_engine::fin_sig_t sig = fin_sig_of(plan);
+        bool device = true;
+        if (!(e->fin_table && e->fin_sig == sig)) {
+            fin_invalidate(e);
+            const int64_t cut = wk_final_host_rows();
+            if (cut > 0) {  // the row count decides: one sync ahead
+                int32_t rc = sync_state_grow(e);
+                if (rc) return rc;
+                synced = true;
+                device = e->nrows >= cut;
+            }
+            if (device) {
+                launch_final(e, plan);
+                int32_t rc = sync_state_grow(e);
+                if (rc) return rc;
+                e->fin_count = (int64_t)e->h_pin[HP_FIN_COUNT];
+                e->fin_table = true;
+                e->fin_sig = sig;
+            }
+        }
+        if (device) {
+            double t0 = now_us();
+            const int64_t rows = e->fin_count;
+            size_t n = (size_t)rows * plan->nrequired;
+            wk_sid_t *res = (wk_sid_t *)malloc(n ? n * 4 : 4);
+            const sid_t *view = e->tbl_view;
+            e->cur ^= 1;
+            e->tbl_view = nullptr;  // the finalized table, for the download only
+            int32_t rc = download_table(e, res, n);
+            e->cur ^= 1;
+            e->tbl_view = view;     // the pre-final table stays current
+            if (rc) { free(res); return rc; }
+            out->col_num = plan->nrequired;
+            out->row_num = rows;
+            out->table = res;
+            out->status_code = 0;
+            if (wk_verbose_lvl() >= 2)
+                fprintf(stderr, "[fetch] rows=%lld final_rows=%lld d2h_us=%.0f\n",
+                        (long long)e->nrows, (long long)rows, now_us() - t0);
+            return WK_OK;
+        }
+    }
     // the device projection writes nrows x nrequired words into the other
     // table buffer, which holds cap_rows x cap_cols: repeated required
     // vars can make nrequired exceed cap_cols (nvars 1, nrequired 8), so
@@ -2207,6 +2412,7 @@ extern "C" int32_t wk_engine_fetch_result(wk_engine_t *e, const wk_plan_t *plan,
         for (int j = 0; j < plan->nrequired; j++)
             cols.c[j] = e->var2col(plan->required_vars[j]);
         sid_t *out_tbl = (sid_t *)e->tbl[e->cur ^ 1].p;
+        fin_invalidate(e);  // a finalized table in that buffer is overwritten
         flush_begin(e);
         TIME_BEGIN(e);
         hipLaunchKernelGGL(k_project, dim3(grid_for(e->cap_rows)), dim3(BLOCK), 0,
@@ -2233,7 +2439,7 @@ extern "C" int32_t wk_engine_fetch_result(wk_engine_t *e, const wk_plan_t *plan,
                     (long long)e->nrows, now_us() - t0);
         return WK_OK;
     }
-    int32_t rc = sync_state_grow(e);
+    int32_t rc = synced ? WK_OK : sync_state_grow(e);
     if (rc) return rc;  // WK_ERR_CAP -> caller re-runs (run_query does)
     if (plan->blind) {
         // Result::blind (query.hpp:321): row count only, no table
@@ -2313,6 +2519,7 @@ static int32_t launch_filter_prog(wk_engine *e, const wk_fnode_t *prog, int n) {
     launch_commit(e);
     e->cur ^= 1;
     e->tbl_view = nullptr;
+    fin_invalidate(e);
     return WK_OK;
 }
 
@@ -2559,9 +2766,12 @@ extern "C" int32_t wk_engine_graph_build(wk_engine_t *e,
                                          int32_t *gid) {
     if (!e || !plan || !gid) return WK_ERR_STATE;
     if (plan->nopt > 0 || plan->nunion > 0) return WK_ERR_PLAN;
-    // replay returns the BLIND row count (pre-DISTINCT/LIMIT): reject
-    // plans whose count the caller would misread
-    if (plan->distinct || plan->limit >= 0 || plan->offset > 0)
+    // replay returns the BLIND row count (pre-DISTINCT/LIMIT); a plan
+    // with final ops ends its chain with the device final pass, whose
+    // count wk_engine_final_count reads.  Without the device pass such a
+    // plan is refused: its caller would misread the count.
+    const bool fin = plan_has_final(plan) && !plan->blind;
+    if (plan_has_final(plan) && (plan->blind || !wk_dev_final()))
         return WK_ERR_PLAN;
     {
         int32_t rc = graph_warm_hints(e, plan, e->capture_hint,
@@ -2576,6 +2786,10 @@ extern "C" int32_t wk_engine_graph_build(wk_engine_t *e,
         return WK_ERR_HIP;
     }
     int32_t rc = wk_engine_submit(e, plan);
+    if (rc == WK_OK && fin) {
+        if (dev_final_ok(e, plan)) launch_final(e, plan);
+        else rc = WK_ERR_PLAN;  // host-only final ops: not replayable
+    }
     if (rc == WK_OK && !e->light)
         launch_publish(e, e->capture_empty_after >= 0);
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
@@ -2601,6 +2815,8 @@ extern "C" int32_t wk_engine_graph_build(wk_engine_t *e,
     wg.bound = e->bound;
     wg.light = e->light;
     wg.view = e->tbl_view;
+    wg.fin = fin;
+    if (fin) wg.fin_sig = fin_sig_of(plan);
     e->graphs.push_back(std::move(wg));
     *gid = (int32_t)e->graphs.size() - 1;
     return WK_OK;
@@ -2622,8 +2838,9 @@ extern "C" int32_t wk_engine_graph_build_suite(wk_engine_t *e,
     std::vector<int> empty_after((size_t)nplans, -1);
     for (int i = 0; i < nplans; i++) {
         const wk_plan_t *plan = &plans[i];
-        if (plan->nopt > 0 || plan->nunion > 0 || plan->distinct ||
-            plan->limit >= 0 || plan->offset > 0)
+        if (plan->nopt > 0 || plan->nunion > 0) return WK_ERR_PLAN;
+        // final-op plans end with the device final pass (graph_build)
+        if (plan_has_final(plan) && (plan->blind || !wk_dev_final()))
             return WK_ERR_PLAN;
         int32_t rc = graph_warm_hints(e, plan, hints[i], &empty_after[i]);
         if (rc) return rc;
@@ -2640,6 +2857,10 @@ extern "C" int32_t wk_engine_graph_build_suite(wk_engine_t *e,
         e->capture_hint = hints[i];
         e->capture_empty_after = empty_after[i];
         rc = wk_engine_submit(e, &plans[i]);
+        if (rc == WK_OK && plan_has_final(&plans[i])) {
+            if (dev_final_ok(e, &plans[i])) launch_final(e, &plans[i]);
+            else rc = WK_ERR_PLAN;
+        }
         if (rc == WK_OK && !e->light)
             launch_publish(e, empty_after[i] >= 0);
     }
@@ -2680,6 +2901,7 @@ extern "C" int32_t wk_engine_graph_launch(wk_engine_t *e, int32_t gid) {
     if (hipGraphLaunch(e->graphs[gid].exec, e->stream) != hipSuccess)
         return WK_ERR_HIP;
     e->zero_pending = false;  // the replay began with its own begin kernel
+    fin_invalidate(e);
     return WK_OK;
 }
 
@@ -2700,6 +2922,7 @@ extern "C" int32_t wk_engine_graph_run(wk_engine_t *e, int32_t gid,
         return WK_ERR_STATE;
     wk_engine::wk_graph &g = e->graphs[gid];
     resolve_timing(e);
+    fin_invalidate(e);
     if (hipGraphLaunch(g.exec, e->stream) != hipSuccess) return WK_ERR_HIP;
     e->zero_pending = false;  // the replay began with its own begin kernel
     HIP_CHECK(stream_sync(e->stream));
@@ -2716,6 +2939,11 @@ extern "C" int32_t wk_engine_graph_run(wk_engine_t *e, int32_t gid,
     }
     e->nrows = (int64_t)e->h_pin[S_NROWS];
     if (nrows) *nrows = e->nrows;
+    if (g.fin) {  // the replay left the finalized table in tbl[cur ^ 1]
+        e->fin_count = (int64_t)e->h_pin[HP_FIN_COUNT];
+        e->fin_table = true;
+        e->fin_sig = g.fin_sig;
+    }
     return WK_OK;
 }
 
