@@ -43,9 +43,10 @@
  *                       evaluation of 4 rows per thread + ballot
  *                       compaction at the widened width (Q1's body)
  *   k_scan_local/mid  — chunked exclusive scan with DEVICE-side length
- *                       (replaces the thrust scans, gpu_hash.cu:587-596);
- *                       k_scan_mid also commits the step (S_INROWS
- *                       snapshot for the scatter side)
+ *                       (replaces the thrust scans, gpu_hash.cu:587-596):
+ *                       several elements per thread, wave scan, one
+ *                       barrier per tile; k_scan_mid also commits the
+ *                       step (S_INROWS snapshot for the scatter side)
  *   k_expand_in/big   — input-centric expansion + wave-per-big-row pass
  *                       (replaces gpu_hash.cu:762-834; no 20-col cap),
  *                       optional inline no-drop typeof verify in graphs
@@ -53,7 +54,8 @@
  *                       map k2u (deg==1 segments; page+value gathers);
  *                       k_expand_fn_map = optimistic 1:1 inside graphs
  *   k_commit, k_set_state, k_begin_state, k_zero_words,
- *   k_publish_state, k_project — 1-thread state kernels, projection.
+ *   k_publish_state, k_publish_begin, k_project — 1-thread state
+ *                       kernels, projection.
  *                       A query's begin zeroing rides on its first state
  *                       write (k_begin_state); the optimistic kernels
  *                       count guard misses into the sticky S_DONE word,
@@ -253,6 +255,10 @@ struct wk_engine {
     // write (k_begin_state) performs it; any other first launch flushes
     // it with k_zero_words (flush_begin)
     bool zero_pending = false;
+    // suite capture: the previous query's publish (value = its
+    // expect_empty; -1 = none), held back so the next query's
+    // k_begin_state can take it along (k_publish_begin)
+    int publish_pending = -1;
     bool hinting = false;  // graph-build hint pass: per-PATTERN row counts
                            // needed, so multi-step fusions are disabled
     int remote_step_idx = -1;  // pattern to run via the xGMI peer path
@@ -399,6 +405,12 @@ static bool wk_row_chain() {  // WK_ROW_CHAIN=0: expansion tails only
 }
 static bool wk_chain() {
     const char *v = getenv("WK_CHAIN");
+    return !(v && !atoi(v));
+}
+// WK_SCAN=0: the barrier-ladder k_scan_local/k_scan_mid (DESIGN.md §3
+// 5g(vi)) in place of the wave-scan ones.  Read per call, like WK_CHAIN.
+static bool wk_wave_scan() {
+    const char *v = getenv("WK_SCAN");
     return !(v && !atoi(v));
 }
 
@@ -918,7 +930,16 @@ extern "C" int32_t wk_engine_begin_query(wk_engine_t *e, const wk_plan_t *plan) 
 // Perform a still-pending begin_query zeroing on its own: called ahead
 // of every launch that reads or publishes d_state and is not itself a
 // begin-aware state write (launch_set_rows).
+// A publish held back by the suite capture goes out on its own when the
+// next query does not open with k_begin_state.
+static void flush_publish(wk_engine *e) {
+    if (e->publish_pending < 0) return;
+    hipLaunchKernelGGL(k_publish_state, dim3(1), dim3(1), 0, e->stream,
+                       e->d_state, e->d_stats, e->h_pin, e->publish_pending);
+    e->publish_pending = -1;
+}
 static void flush_begin(wk_engine *e) {
+    flush_publish(e);
     if (!e->zero_pending) return;
     e->zero_pending = false;
     hipLaunchKernelGGL(k_zero_words, dim3(1), dim3(64), 0, e->stream, e->d_state,
@@ -929,11 +950,18 @@ static void flush_begin(wk_engine *e) {
 // also does begin_query's zeroing (one kernel); later it keeps
 // k_set_state's meaning and leaves S_ERR/S_REQ/S_DONE alone.
 static void launch_set_rows(wk_engine *e, uint64_t nrows) {
-    if (e->zero_pending) {
+    if (e->zero_pending && e->publish_pending >= 0) {
+        e->zero_pending = false;
+        hipLaunchKernelGGL(k_publish_begin, dim3(1), dim3(1), 0, e->stream,
+                           e->d_state, e->d_stats, e->h_pin,
+                           e->publish_pending, nrows);
+        e->publish_pending = -1;
+    } else if (e->zero_pending) {
         e->zero_pending = false;
         hipLaunchKernelGGL(k_begin_state, dim3(1), dim3(1), 0, e->stream,
                            e->d_state, nrows);
     } else {
+        flush_publish(e);
         hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream,
                            e->d_state, nrows);
     }
@@ -1240,7 +1268,8 @@ static void launch_filter_tpr(wk_engine *e, const fparams &P, int verify_only,
 }
 
 static void launch_scan_mid(wk_engine *e, int G) {
-    hipLaunchKernelGGL(k_scan_mid, dim3(1), dim3(SCAN_T), 0, e->stream,
+    hipLaunchKernelGGL(wk_wave_scan() ? k_scan_mid : k_scan_mid_ladder,
+                       dim3(1), dim3(SCAN_T), 0, e->stream,
                        (uint64_t *)e->bsums.p, G, (uint64_t)e->cap_rows,
                        e->d_state);
 }
@@ -1255,7 +1284,8 @@ static void launch_gather_scan(wk_engine *e, int G, bool timed,
                                Gather &&gather) {
     auto front = [&] {
         gather();
-        hipLaunchKernelGGL(k_scan_local, dim3(G), dim3(SCAN_T), 0, e->stream,
+        hipLaunchKernelGGL(wk_wave_scan() ? k_scan_local : k_scan_local_ladder,
+                           dim3(G), dim3(SCAN_T), 0, e->stream,
                            (const uint32_t *)e->cnt.p, e->d_state,
                            (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p);
     };
@@ -2648,6 +2678,7 @@ extern "C" int32_t wk_engine_submit(wk_engine_t *e, const wk_plan_t *plan) {
         uint64_t off = ptr ? (uint64_t)(ptr - e->st->edges.data()) : 0;
         rc = grow_caps(e, (int64_t)sz, e->nvars);
         if (rc) return rc;
+        flush_publish(e);
         TIME_BEGIN(e);
         hipLaunchKernelGGL(k_light2, dim3(1), dim3(BLOCK), 0, e->stream,
                            e->d_edges, off, sz, (sid_t)plan->patterns[1].object,
@@ -2746,20 +2777,39 @@ static int32_t graph_warm_hints(wk_engine *e, const wk_plan_t *plan,
     return WK_OK;
 }
 
+// WK_FUSE_PAIR=0: suite captures keep k_publish_state + k_begin_state
+// as two launches between queries.  Read per call, like WK_CHAIN.
+static bool wk_fuse_pair() {
+    const char *v = getenv("WK_FUSE_PAIR");
+    return !(v && !atoi(v));
+}
+// True when the plan's first launch in a capture is the begin-aware state
+// write of step_start (exec_pattern's `start` at step 0): an index or
+// constant start whose row count the host knows.  k_light2 plans begin
+// and publish inside their one kernel.
+static bool opens_with_begin_state(wk_engine *e, const wk_plan_t *plan) {
+    if (plan->npatterns <= 0 || light2_eligible(e, plan)) return false;
+    if (e->remote_step_idx == 0) return false;
+    const wk_pattern_t &p = plan->patterns[0];
+    return p.predicate >= 0 && p.subject >= 0 &&
+           (is_tpid(p.subject) || p.object < 0);
+}
+
 static void end_capture_state(wk_engine *e) {
     e->capturing = 0;
+    e->publish_pending = -1;
     e->capture_hint.clear();
     e->capture_empty_after = -1;
 }
 
 // ---------------------------------------------------------------------
 // hipGraph replay of a whole fixed plan: the benchmark suite re-runs
-// the same 7 queries every step, so the ~20-launch chain (with its
-// per-launch dispatch gaps) collapses into ONE hipGraphLaunch.  Build
-// captures the submit chain (after a warm pass settles capacities —
-// growth is illegal mid-capture); run replays it and returns the blind
-// row count.  S_ERR on replay = capacity overflow: caller falls back
-// to the plain submit path.
+// the same 7 queries every step, so each plan's launch chain (3 to 12
+// dispatches, with its per-launch dispatch gaps) collapses into ONE
+// hipGraphLaunch.  Build captures the submit chain (after a warm pass
+// settles capacities — growth is illegal mid-capture); run replays it
+// and returns the blind row count.  S_ERR on replay = capacity
+// overflow: caller falls back to the plain submit path.
 // ---------------------------------------------------------------------
 extern "C" int32_t wk_engine_graph_build(wk_engine_t *e,
                                          const wk_plan_t *plan,
@@ -2861,9 +2911,19 @@ extern "C" int32_t wk_engine_graph_build_suite(wk_engine_t *e,
             if (dev_final_ok(e, &plans[i])) launch_final(e, &plans[i]);
             else rc = WK_ERR_PLAN;
         }
-        if (rc == WK_OK && !e->light)
-            launch_publish(e, empty_after[i] >= 0);
+        if (rc == WK_OK && !e->light) {
+            // the next query opens with k_begin_state(host-known rows):
+            // hold this publish back for it (k_publish_begin)
+            if (i + 1 < nplans && wk_fuse_pair() &&
+                opens_with_begin_state(e, &plans[i + 1])) {
+                flush_begin(e);
+                e->publish_pending = empty_after[i] >= 0;
+            } else {
+                launch_publish(e, empty_after[i] >= 0);
+            }
+        }
     }
+    if (rc == WK_OK) flush_publish(e);  // never left pending: see above
     hipError_t ce = hipStreamEndCapture(e->stream, &g);
     end_capture_state(e);
     if (rc != WK_OK || ce != hipSuccess || !g) {

@@ -589,12 +589,87 @@ k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
     }
 }
 
+// inclusive scan of one u64 per lane across the 64-lane wave (6 cross-
+// lane steps, no LDS, no barrier)
+__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, int lane) {
+#pragma unroll
+    for (int ofs = 1; ofs < 64; ofs <<= 1) {
+        const uint64_t t = __shfl_up((unsigned long long)v, ofs);
+        if (lane >= ofs) v += t;
+    }
+    return v;
+}
+
+// Block-wide exclusive offset of this thread's `tsum` among the SCAN_T
+// threads, plus the block total: wave scan in registers, the SCAN_T/64
+// wave totals through LDS, ONE barrier.  s_wtot is the caller's
+// [2][SCAN_T/64] ping-pong (`par` = tile parity), which is what makes a
+// single barrier per tile enough: a wave can only reach the tile that
+// rewrites a slot after passing the barrier of the tile in between,
+// i.e. after every wave has read that slot.
+__device__ __forceinline__ uint64_t block_excl_scan(uint64_t tsum,
+                                                    uint64_t (*s_wtot)[SCAN_T / 64],
+                                                    int par, uint64_t *total) {
+    static_assert(SCAN_T == 256, "four wave totals");
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const uint64_t incl = wave_incl_scan(tsum, lane);
+    if (lane == 63) s_wtot[par][wid] = incl;
+    __syncthreads();
+    const uint64_t w0 = s_wtot[par][0], w1 = s_wtot[par][1],
+                   w2 = s_wtot[par][2], w3 = s_wtot[par][3];
+    const uint64_t wbase = (wid > 0 ? w0 : 0) + (wid > 1 ? w1 : 0) +
+                           (wid > 2 ? w2 : 0);
+    *total = w0 + w1 + w2 + w3;
+    return wbase + incl - tsum;
+}
+
 // chunked exclusive prefix of d_cnt -> d_pre + per-chunk sums (same
-// chunk math as k_probe_scan so the expansion kernels are unchanged)
-__global__ void k_scan_local(const uint32_t *__restrict__ d_cnt,
-                             const uint64_t *__restrict__ d_state,
-                             uint64_t *__restrict__ d_pre,
-                             uint64_t *__restrict__ bsums)
+// chunk math as k_probe_scan so the expansion kernels are unchanged).
+// Each thread owns SCAN_PER consecutive rows and sums them in registers;
+// one barrier per SCAN_T*SCAN_PER-row tile (block_excl_scan).
+constexpr int SCAN_PER = 4;
+__global__ void __launch_bounds__(SCAN_T)
+k_scan_local(const uint32_t *__restrict__ d_cnt,
+             const uint64_t *__restrict__ d_state,
+             uint64_t *__restrict__ d_pre, uint64_t *__restrict__ bsums)
+{
+    const int64_t nrows = (int64_t)d_state[S_NROWS];
+    const int G = gridDim.x;
+    const int64_t chunk = (nrows + G - 1) / G;
+    const int64_t start = (int64_t)blockIdx.x * chunk;
+    const int64_t end = min(start + chunk, (int64_t)nrows);
+    __shared__ uint64_t s_wtot[2][SCAN_T / 64];
+    uint64_t carry = 0;
+    int par = 0;
+    for (int64_t base = start; base < end;
+         base += SCAN_T * SCAN_PER, par ^= 1) {
+        const int64_t r0 = base + (int64_t)threadIdx.x * SCAN_PER;
+        const uint32_t c0 = (r0 < end) ? d_cnt[r0] : 0u;
+        const uint32_t c1 = (r0 + 1 < end) ? d_cnt[r0 + 1] : 0u;
+        const uint32_t c2 = (r0 + 2 < end) ? d_cnt[r0 + 2] : 0u;
+        const uint32_t c3 = (r0 + 3 < end) ? d_cnt[r0 + 3] : 0u;
+        uint64_t total;
+        uint64_t pre = carry + block_excl_scan((uint64_t)c0 + c1 + c2 + c3,
+                                               s_wtot, par, &total);
+        if (r0 < end) d_pre[r0] = pre;
+        pre += c0;
+        if (r0 + 1 < end) d_pre[r0 + 1] = pre;
+        pre += c1;
+        if (r0 + 2 < end) d_pre[r0 + 2] = pre;
+        pre += c2;
+        if (r0 + 3 < end) d_pre[r0 + 3] = pre;
+        carry += total;
+    }
+    if (threadIdx.x == 0) bsums[blockIdx.x] = (start < end) ? carry : 0;
+}
+
+// WK_SCAN=0: the previous Hillis-Steele ladders (one element per thread
+// in LDS, ~18 barriers per SCAN_T elements), kept so the rewrite can be
+// timed alone.  Same arguments, launch shape and outputs.
+__global__ void k_scan_local_ladder(const uint32_t *__restrict__ d_cnt,
+                                    const uint64_t *__restrict__ d_state,
+                                    uint64_t *__restrict__ d_pre,
+                                    uint64_t *__restrict__ bsums)
 {
     const int64_t nrows = (int64_t)d_state[S_NROWS];
     const int G = gridDim.x;
@@ -655,8 +730,55 @@ __global__ void k_fn_scatter(const sid_t *__restrict__ tbl,
 // the INPUT row count from the S_INROWS snapshot, and S_OVF (the
 // big-row queue this chain is about to fill) starts clean — saving
 // the separate 1-thread commit launch per k2u/fn step.
-__global__ void k_scan_mid(uint64_t *__restrict__ bsums, int G,
-                           uint64_t cap, uint64_t *__restrict__ d_state)
+__device__ __forceinline__ void scan_mid_commit(uint64_t *__restrict__ d_state,
+                                                uint64_t t, uint64_t cap) {
+    d_state[S_INROWS] = d_state[S_NROWS];
+    if (t > cap) {
+        d_state[S_ERR] = 1;
+        d_state[S_REQ] = max(d_state[S_REQ], t);
+        t = cap;
+    }
+    d_state[S_NROWS] = t;
+    d_state[S_TOTAL] = 0;
+    d_state[S_OVF] = 0;
+}
+
+// Each thread owns per = ceil(G/SCAN_T) (at most SCAN_MID_PER)
+// consecutive sums in registers; one barrier per tile (block_excl_scan).
+// scan_grid caps G at SCAN_T*SCAN_MID_PER, so the tile loop runs once.
+constexpr int SCAN_MID_PER = 8;
+__global__ void __launch_bounds__(SCAN_T)
+k_scan_mid(uint64_t *__restrict__ bsums, int G, uint64_t cap,
+           uint64_t *__restrict__ d_state)
+{
+    __shared__ uint64_t s_wtot[2][SCAN_T / 64];
+    const int per = min((G + SCAN_T - 1) / SCAN_T, SCAN_MID_PER);
+    uint64_t carry = 0;
+    int par = 0;
+    for (int base = 0; base < G; base += SCAN_T * per, par ^= 1) {
+        const int i0 = base + (int)threadIdx.x * per;
+        uint64_t v[SCAN_MID_PER];  // fully unrolled: stays in registers
+        uint64_t tsum = 0;
+#pragma unroll
+        for (int k = 0; k < SCAN_MID_PER; k++) {
+            v[k] = (k < per && i0 + k < G) ? bsums[i0 + k] : 0;
+            tsum += v[k];
+        }
+        uint64_t total;
+        uint64_t pre = carry + block_excl_scan(tsum, s_wtot, par, &total);
+#pragma unroll
+        for (int k = 0; k < SCAN_MID_PER; k++) {
+            if (k < per && i0 + k < G) bsums[i0 + k] = pre;
+            pre += v[k];
+        }
+        carry += total;
+    }
+    if (threadIdx.x == 0) scan_mid_commit(d_state, carry, cap);
+}
+
+// WK_SCAN=0 sibling of k_scan_mid (see k_scan_local_ladder)
+__global__ void k_scan_mid_ladder(uint64_t *__restrict__ bsums, int G,
+                                  uint64_t cap, uint64_t *__restrict__ d_state)
 {
     __shared__ uint64_t sh[SCAN_T];
     uint64_t carry = 0;
@@ -747,10 +869,10 @@ __global__ void k_project(const sid_t *__restrict__ tbl, int ncols,
 // copied out.  expect_empty (captured plans with a truncated empty
 // tail): the skipped patterns are only valid on an empty table, so any
 // row left raises S_ERR the same way.
-__global__ void k_publish_state(uint64_t *__restrict__ d_state,
-                                const uint64_t *__restrict__ d_stats,
-                                uint64_t *__restrict__ h_pin,
-                                int expect_empty) {
+__device__ __forceinline__ void publish_state(uint64_t *__restrict__ d_state,
+                                              const uint64_t *__restrict__ d_stats,
+                                              uint64_t *__restrict__ h_pin,
+                                              int expect_empty) {
     if (d_state[S_DONE] || (expect_empty && d_state[S_NROWS])) {
         d_state[S_ERR] = 1;
         d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
@@ -761,6 +883,25 @@ __global__ void k_publish_state(uint64_t *__restrict__ d_state,
     // graph replays whose own begin kernels clear d_state — the
     // one-sync-per-pass path checks and clears it host-side
     if (d_state[S_ERR]) h_pin[7] = 1;
+}
+__global__ void k_publish_state(uint64_t *__restrict__ d_state,
+                                const uint64_t *__restrict__ d_stats,
+                                uint64_t *__restrict__ h_pin,
+                                int expect_empty) {
+    publish_state(d_state, d_stats, h_pin, expect_empty);
+}
+
+// Suite captures: query i's publish followed by query i+1's begin, the
+// same writes in the same order from one thread — one launch for two
+// 
+__global__ void k_publish_begin(uint64_t *__restrict__ d_state,
+                                const uint64_t *__restrict__ d_stats,
+                                uint64_t *__restrict__ h_pin,
+                                int expect_empty, uint64_t nrows) {
+    publish_state(d_state, d_stats, h_pin, expect_empty);
+#pragma unroll
+    for (int i = 0; i < S_WORDS; i++) d_state[i] = 0;
+    d_state[S_NROWS] = nrows;
 }
 
 // Input-centric expansion (known_to_unknown back half,
