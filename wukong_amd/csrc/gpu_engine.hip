@@ -20,7 +20,8 @@
  *   probe_one/probe_chain, bsearch_u32, tbm_has, csr_entry,
  *   typeof_nodrop_ok — lookup helpers; d_state words and categories;
  *   chain_eval (row-major, early exit) and chain_eval_batch (op-major,
- *   K candidates, no early exit) — the per-row op chain evaluators
+ *   K candidates of compile-time width W, no early exit) — the per-row
+ *   op chain evaluators
  *  wk_kernels_expand.h
  *   k_probe_scan      — fused gen-keys + thread-per-row cluster-hash
  *                       probe + in-kernel prefix scan (2-deep bucket
@@ -42,6 +43,10 @@
  *                       in front as ONE pass over the table: op-major
  *                       evaluation of 4 rows per thread + ballot
  *                       compaction at the widened width (Q1's body)
+ *                       (k_row_chain, k_csr_gather_chain, k_expand_chain
+ *                       are instantiated <NC, W>: candidate rows are 4
+ *                       columns wide when the plan's widened row fits,
+ *                       else 8; WK_CHAIN_WIDTH=8 forces 8)
  *   k_scan_local/mid  — chunked exclusive scan with DEVICE-side length
  *                       (replaces the thrust scans, gpu_hash.cu:587-596):
  *                       several elements per thread, wave scan, one
@@ -66,7 +71,10 @@
  *   k_filter_tpr      — fused probe/typeof filter + block compaction
  *                       (replaces gpu_hash.cu:326-445,523-585);
  *                       per-type bitmaps: rdf:type filters read
- *                       1 bit/vid (LLC-resident)
+ *                       1 bit/vid (LLC-resident); the bitmap, PM_EQ and
+ *                       functional-map paths evaluate a thread's 4 rows
+ *                       op-major (filter_keep_batch; WK_FILTER_BATCH=0:
+ *                       row after row)
  *   k_filter_expr     — FILTER expressions (=, !=, bound, &&, ||, !) as a
  *                       postfix program with a register bit-stack, same
  *                       compaction; pushed down behind the pattern that
@@ -405,6 +413,20 @@ static bool wk_row_chain() {  // WK_ROW_CHAIN=0: expansion tails only
 }
 static bool wk_chain() {
     const char *v = getenv("WK_CHAIN");
+    return !(v && !atoi(v));
+}
+// Width bucket of the batched chain kernels: candidate
+// rows are carried as sid_t[ROW_NARROW] when the plan's widened row fits,
+// else as sid_t[ROW_MAX].  WK_CHAIN_WIDTH=8 forces the wide instantiation
+// (A/B arm and fallback).  Read per call, like WK_CHAIN.
+static bool chain_narrow(int out_cols) {
+    const char *v = getenv("WK_CHAIN_WIDTH");
+    return out_cols <= ROW_NARROW && !(v && atoi(v) == ROW_MAX);
+}
+// WK_FILTER_BATCH=0: k_filter_tpr evaluates its rows one after another
+// (filter_keep) on every path.  Read per call, like WK_CHAIN.
+static bool wk_filter_batch() {
+    const char *v = getenv("WK_FILTER_BATCH");
     return !(v && !atoi(v));
 }
 // WK_SCAN=0: the barrier-ladder k_scan_local/k_scan_mid (DESIGN.md §3
@@ -1263,8 +1285,8 @@ static fparams fparams_list(const wk_engine *e, const sid_t *edges,
 static void launch_filter_tpr(wk_engine *e, const fparams &P, int verify_only,
                               sid_t *out_tbl) {
     hipLaunchKernelGGL(k_filter_tpr, dim3(grid_for(e->bound)), dim3(BLOCK), 0,
-                       e->stream, P, verify_only, e->d_state, e->d_stats,
-                       out_tbl);
+                       e->stream, P, verify_only, (int)wk_filter_batch(),
+                       e->d_state, e->d_stats, out_tbl);
 }
 
 static void launch_scan_mid(wk_engine *e, int G) {
@@ -1857,42 +1879,55 @@ static int32_t step_k2u_classic(wk_engine *e, const step_ctx &c,
 
 // The same exact pipeline with a per-row op chain as the per-edge
 // predicate: consumes the k2u and the chain's patterns.
+// NC input columns, candidates W wide (chain_narrow picks the bucket).
+template <int NC, int W>
+static void launch_k2u_chain(wk_engine *e, const step_ctx &c,
+                             const fnpage_t *c_pg, const chain_plan &cp,
+                             int G) {
+    const wk_store *st = e->st;
+    launch_gather_scan(e, G, /*timed*/ true, [&] {
+        hipLaunchKernelGGL(
+            (k_csr_gather_chain<NC, W>), dim3(grid_for(e->bound)),
+            dim3(BLOCK), 0, e->stream, c.cur_tbl, c.col, c_pg,
+            e->gs->d_csr_entries[(size_t)c.p * 2 + c.dir], st->fn_base,
+            st->fn_n, e->d_edges, cp.C, e->d_state, e->d_stats,
+            (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p,
+            (uint32_t *)e->pmask.p);
+    });
+    TIME_BEGIN(e);
+    hipLaunchKernelGGL(
+        (k_expand_chain<NC, W>), dim3(grid_for(e->bound)), dim3(BLOCK), 0,
+        e->stream, c.cur_tbl, e->d_edges, (uint64_t *)e->eoff.p,
+        (uint32_t *)e->cnt.p, (uint32_t *)e->pmask.p,
+        (uint64_t *)e->prefix.p,
+        (uint64_t *)e->bsums.p, G, cp.C, cp.out_cols, e->d_state,
+        (uint64_t)e->cap_rows, e->d_stats, (uint32_t *)e->ovf.p,
+        c.out_tbl);
+    hipLaunchKernelGGL(
+        k_expand_chain_big<NC>, dim3(512), dim3(BLOCK), 0, e->stream,
+        c.cur_tbl, e->d_edges, (uint64_t *)e->eoff.p,
+        (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p, G, cp.C,
+        cp.out_cols, e->d_state, (uint64_t)e->cap_rows,
+        (uint32_t *)e->ovf.p, c.out_tbl);
+    TIME_END(e, CAT_EXPAND);
+}
 static int32_t step_k2u_chain(wk_engine *e, const step_ctx &c,
                               const fnpage_t *c_pg, const chain_plan &cp) {
-    const wk_store *st = e->st;
     const int G = scan_grid(e->bound);
     const int nc_in = e->ncols;
     // the edge value needs a column of its own (step_k2u checked cap_cols)
     if (nc_in + 1 > ROW_MAX) return WK_ERR_STATE;
+    const bool narrow = chain_narrow(cp.out_cols);
     with_ncols(nc_in, [&](auto nc) {
         constexpr int NC = decltype(nc)::value;
-        if constexpr (NC < ROW_MAX) {
-            launch_gather_scan(e, G, /*timed*/ true, [&] {
-                hipLaunchKernelGGL(
-                    k_csr_gather_chain<NC>, dim3(grid_for(e->bound)),
-                    dim3(BLOCK), 0, e->stream, c.cur_tbl, c.col, c_pg,
-                    e->gs->d_csr_entries[(size_t)c.p * 2 + c.dir], st->fn_base,
-                    st->fn_n, e->d_edges, cp.C, e->d_state, e->d_stats,
-                    (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p,
-                    (uint32_t *)e->pmask.p);
-            });
-            TIME_BEGIN(e);
-            hipLaunchKernelGGL(
-                k_expand_chain<NC>, dim3(grid_for(e->bound)), dim3(BLOCK), 0,
-                e->stream, c.cur_tbl, e->d_edges, (uint64_t *)e->eoff.p,
-                (uint32_t *)e->cnt.p, (uint32_t *)e->pmask.p,
-                (uint64_t *)e->prefix.p,
-                (uint64_t *)e->bsums.p, G, cp.C, cp.out_cols, e->d_state,
-                (uint64_t)e->cap_rows, e->d_stats, (uint32_t *)e->ovf.p,
-                c.out_tbl);
-            hipLaunchKernelGGL(
-                k_expand_chain_big<NC>, dim3(512), dim3(BLOCK), 0, e->stream,
-                c.cur_tbl, e->d_edges, (uint64_t *)e->eoff.p,
-                (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p, G, cp.C,
-                cp.out_cols, e->d_state, (uint64_t)e->cap_rows,
-                (uint32_t *)e->ovf.p, c.out_tbl);
-            TIME_END(e, CAT_EXPAND);
+        if constexpr (NC < ROW_NARROW) {
+            if (narrow) {
+                launch_k2u_chain<NC, ROW_NARROW>(e, c, c_pg, cp, G);
+                return;
+            }
         }
+        if constexpr (NC < ROW_MAX)
+            launch_k2u_chain<NC, ROW_MAX>(e, c, c_pg, cp, G);
     });
     bind_chain_vars(e, cp, nc_in + 1);
     finish_step(e, c.o, cp.out_cols, e->cap_rows, 1 + cp.npat);
@@ -1905,16 +1940,28 @@ static int32_t step_k2u_chain(wk_engine *e, const step_ctx &c,
 // consumed patterns and nothing counts into S_DONE, so inside a capture
 // it replaces the optimistic 1:1 maps and verify-only filters it covers.
 // Output rows <= input rows; e->bound is unchanged.
+template <int NC, int W>
+static void launch_row_chain(wk_engine *e, const step_ctx &c,
+                             const chain_plan &cp) {
+    hipLaunchKernelGGL((k_row_chain<NC, W>), dim3(grid_for(e->bound)),
+                       dim3(BLOCK), 0, e->stream, c.cur_tbl, cp.C,
+                       cp.out_cols, e->d_state, (uint64_t)e->cap_rows,
+                       e->d_stats, c.out_tbl);
+}
 static int32_t step_row_chain(wk_engine *e, const step_ctx &c,
                               const chain_plan &cp) {
     const int nc_in = e->ncols;
+    const bool narrow = chain_narrow(cp.out_cols);
     TIME_BEGIN(e);
     with_ncols(nc_in, [&](auto nc) {
         constexpr int NC = decltype(nc)::value;
-        hipLaunchKernelGGL(k_row_chain<NC>, dim3(grid_for(e->bound)),
-                           dim3(BLOCK), 0, e->stream, c.cur_tbl, cp.C,
-                           cp.out_cols, e->d_state, (uint64_t)e->cap_rows,
-                           e->d_stats, c.out_tbl);
+        if constexpr (NC <= ROW_NARROW) {
+            if (narrow) {
+                launch_row_chain<NC, ROW_NARROW>(e, c, cp);
+                return;
+            }
+        }
+        launch_row_chain<NC, ROW_MAX>(e, c, cp);
     });
     TIME_END(e, CAT_FILTER);
     launch_commit(e);

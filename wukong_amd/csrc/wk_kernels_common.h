@@ -94,6 +94,9 @@ enum { CH_FN_APPEND = 0,  // v = fn[row[a]]; 0 drops, else append v
        CH_EQ = 3 };       // row[a] == cval                 (PM_EQ k2c)
 constexpr int CHAIN_MAX = 8;  // ops per chain
 constexpr int ROW_MAX = 8;    // wk_engine_begin_query rejects nvars > 8
+// narrow width bucket of the batched chain kernels: candidates of a plan
+// whose out_cols <= ROW_NARROW are carried as sid_t[ROW_NARROW]
+constexpr int ROW_NARROW = 4;
 // batched chain evaluation in the fused expansion: edges of one row per
 // round (LUBM takesCourse degrees are 2-4) x rows walked side by side
 constexpr int CHAIN_EK = 4;
@@ -119,9 +122,11 @@ __device__ __forceinline__ sid_t row_get(const sid_t (&row)[ROW_MAX], int c) {
     for (int i = 1; i < ROW_MAX; i++) v = (c == i) ? row[i] : v;
     return v;
 }
-__device__ __forceinline__ void row_set(sid_t (&row)[ROW_MAX], int c, sid_t v) {
+// (W: the row's compile-time width, ROW_MAX or the plan's width bucket)
+template <int W>
+__device__ __forceinline__ void row_set(sid_t (&row)[W], int c, sid_t v) {
 #pragma unroll
-    for (int i = 0; i < ROW_MAX; i++) row[i] = (c == i) ? v : row[i];
+    for (int i = 0; i < W; i++) row[i] = (c == i) ? v : row[i];
 }
 
 // Evaluate the chain on a row whose first NC columns are valid; appended
@@ -158,12 +163,13 @@ __device__ __forceinline__ bool chain_eval(const chain_t &C,
 // Column pick for the batched evaluator.  Same contract as row_get, but
 // built from AND/OR masks: a chain of selects between two loaded columns
 // can be rewritten by the optimiser into ONE load at a selected address
-// while the K x ROW_MAX candidate array still lives in memory, which then
+// while the K x W candidate array still lives in memory, which then
 // never becomes registers (observed: 144-400 B of scratch per lane).
-__device__ __forceinline__ sid_t row_pick(const sid_t (&row)[ROW_MAX], int c) {
+template <int W>
+__device__ __forceinline__ sid_t row_pick(const sid_t (&row)[W], int c) {
     sid_t v = 0;
 #pragma unroll
-    for (int i = 0; i < ROW_MAX; i++) v |= row[i] & (0u - (sid_t)(c == i));
+    for (int i = 0; i < W; i++) v |= row[i] & (0u - (sid_t)(c == i));
     return v;
 }
 
@@ -180,10 +186,14 @@ __device__ __forceinline__ sid_t row_pick(const sid_t (&row)[ROW_MAX], int c) {
 // candidate.  Keep/drop and the appended columns are exactly chain_eval's.
 // APPEND_ONLY: the candidates are known to pass (the count pass said so);
 // only the FN_APPEND lookups are repeated, the filter ops are skipped.
-template <int NC, int K, bool APPEND_ONLY = false>
+// W is the candidates' compile-time width: the host picks the bucket that
+// holds the plan's out_cols (chain_width), so every column an op reads or
+// appends is below W, and the picks and sets cost W selects, not ROW_MAX.
+template <int NC, int K, bool APPEND_ONLY = false, int W = ROW_MAX>
 __device__ __forceinline__ uint32_t chain_eval_batch(
-    const chain_t &C, sid_t (&rows)[K][ROW_MAX], uint32_t active) {
+    const chain_t &C, sid_t (&rows)[K][W], uint32_t active) {
     static_assert(K >= 1 && K <= 32, "keep mask is 32 bits");
+    static_assert(NC <= W && W <= ROW_MAX, "the input columns must fit");
     uint32_t keep = active;
     int nc = NC;
     // the op loop stays rolled: one op's parameters are read from the

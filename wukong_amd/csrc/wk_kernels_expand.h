@@ -288,7 +288,10 @@ __global__ void k_expand_tf_big(const sid_t *__restrict__ tbl, int ncols,
 // leaves a 32-bit pass mask per row (bit k = edge k passes) in d_pmask,
 // so the writer of a <= 32-edge row takes the passing edges from the
 // mask and repeats only the chain's FN_APPEND lookups.
-template <int NC>
+// W (here and in k_expand_chain, k_row_chain) is the candidate rows'
+// compile-time width, the bucket that holds the plan's out_cols: the
+// candidate array and every column pick / set scale with it.
+template <int NC, int W>
 __global__ void __launch_bounds__(SCAN_T)
 k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
                                    const fnpage_t *__restrict__ pg,
@@ -302,7 +305,7 @@ k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
                                    uint32_t *__restrict__ d_cnt,
                                    uint32_t *__restrict__ d_pmask)
 {
-    static_assert(NC < ROW_MAX, "the edge value needs a column");
+    static_assert(NC < W && W <= ROW_MAX, "the edge value needs a column");
     static_assert(32 % CHAIN_EK == 0, "pass-mask groups must tile 32 bits");
     constexpr int RPT = CHAIN_RPT, EK = CHAIN_EK, K = RPT * EK;
     const int64_t nrows = (int64_t)d_state[S_NROWS];
@@ -342,7 +345,7 @@ k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
             maxlen = max(maxlen, len[q]);
         }
         for (uint32_t k0 = 0; k0 < maxlen; k0 += EK) {
-            sid_t cand[K][ROW_MAX];
+            sid_t cand[K][W];
             uint32_t active = 0;
 #pragma unroll
             for (int q = 0; q < RPT; q++) {
@@ -352,7 +355,7 @@ k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
                     const bool on = k0 + j < len[q];
                     active |= on ? 1u << (q * EK + j) : 0u;
 #pragma unroll
-                    for (int c = 0; c < ROW_MAX; c++) cand[q * EK + j][c] = 0;
+                    for (int c = 0; c < W; c++) cand[q * EK + j][c] = 0;
 #pragma unroll
                     for (int c = 0; c < NC; c++)
                         cand[q * EK + j][c] = in[q][c];
@@ -384,7 +387,7 @@ k_csr_gather_chain(const sid_t *__restrict__ tbl, int col,
 // writer: emit the passing (widened) rows at the exact scanned positions,
 // taking the passing edges from the count pass's mask; rows with > 32
 // edges go to the wave pass, which re-evaluates the chain
-template <int NC>
+template <int NC, int W>
 __global__ void __launch_bounds__(SCAN_T)
 k_expand_chain(const sid_t *__restrict__ tbl,
                                const sid_t *__restrict__ edges,
@@ -399,7 +402,7 @@ k_expand_chain(const sid_t *__restrict__ tbl,
                                uint32_t *__restrict__ ovf,
                                sid_t *__restrict__ out)
 {
-    static_assert(NC < ROW_MAX, "the edge value needs a column");
+    static_assert(NC < W && W <= ROW_MAX, "the edge value needs a column");
     constexpr int EK = CHAIN_EK;
     const int64_t nrows = (int64_t)d_state[S_INROWS];
     const int64_t chunk = (nrows + G - 1) / G;
@@ -427,7 +430,7 @@ k_expand_chain(const sid_t *__restrict__ tbl,
         // loaded together, and so are the FN_APPEND lookups of a chain
         // that widens the row (off is valid: keep > 0 means len > 0)
         for (uint32_t m = d_pmask[r]; m;) {
-            sid_t cand[EK][ROW_MAX];
+            sid_t cand[EK][W];
             uint32_t act = 0;
 #pragma unroll
             for (int j = 0; j < EK; j++) {
@@ -436,7 +439,7 @@ k_expand_chain(const sid_t *__restrict__ tbl,
                 m &= m - 1;
                 act |= on ? 1u << j : 0u;
 #pragma unroll
-                for (int c = 0; c < ROW_MAX; c++) cand[j][c] = 0;
+                for (int c = 0; c < W; c++) cand[j][c] = 0;
 #pragma unroll
                 for (int c = 0; c < NC; c++) cand[j][c] = in[c];
                 cand[j][NC] = edges[off + p];
@@ -447,7 +450,7 @@ k_expand_chain(const sid_t *__restrict__ tbl,
             for (int j = 0; j < EK; j++) {
                 if (((act >> j) & 1) && basep + w < cap) {
 #pragma unroll
-                    for (int c = 0; c < ROW_MAX; c++)
+                    for (int c = 0; c < W; c++)
                         if (c < oc) dst[c] = cand[j][c];
                     dst += oc;
                     w++;
@@ -525,12 +528,13 @@ __global__ void k_expand_chain_big(const sid_t *__restrict__ tbl,
 // compacted at the widened width with k_filter_tpr's ballot ranks (one
 // LDS atomic per wave, one S_TOTAL atomic per 1024-row tile); k_commit
 // follows.  Exact; nothing counts into S_DONE.
-template <int NC>
+template <int NC, int W>
 __global__ void __launch_bounds__(SCAN_T)
 k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
             uint64_t *__restrict__ d_state, uint64_t cap,
             uint64_t *__restrict__ d_stats, sid_t *__restrict__ out)
 {
+    static_assert(NC <= W && W <= ROW_MAX, "the input columns must fit");
     constexpr int K = 4;
     const int64_t nrows = (int64_t)d_state[S_NROWS];
     count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * (4 * NC + 4 * oc));
@@ -543,7 +547,7 @@ k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
     const int64_t stride = (int64_t)gridDim.x * tile;
     for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows;
          base += stride) {
-        sid_t rows[K][ROW_MAX];
+        sid_t rows[K][W];
         uint32_t active = 0;
 #pragma unroll
         for (int k = 0; k < K; k++) {
@@ -552,7 +556,7 @@ k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
             const int64_t rr = in ? r : base;  // base < nrows: a valid row
             active |= in ? 1u << k : 0u;
 #pragma unroll
-            for (int c = 0; c < ROW_MAX; c++) rows[k][c] = 0;
+            for (int c = 0; c < W; c++) rows[k][c] = 0;
 #pragma unroll
             for (int c = 0; c < NC; c++) rows[k][c] = tbl[rr * NC + c];
         }
@@ -581,7 +585,7 @@ k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
             if (((keep >> k) & 1) && pos < cap) {  // past cap: k_commit flags
                 sid_t *dst = out + (int64_t)pos * oc;
 #pragma unroll
-                for (int c = 0; c < ROW_MAX; c++)
+                for (int c = 0; c < W; c++)
                     if (c < oc) dst[c] = rows[k][c];
             }
             wpos += (uint32_t)__popcll(mask[k]);

@@ -64,6 +64,102 @@ __device__ __forceinline__ bool filter_keep(const fparams &P, int64_t r) {
     return esz && bsearch_u32(P.edges + eoff, esz, tgt);
 }
 
+// The keep paths of filter_keep that are plain gathers, which
+// filter_keep_batch evaluates op-major; FB_NONE = per-row filter_keep
+// (dense type_of with its 0xFFFF probe fallback, PM_LIST, the cluster-hash
+// probe, and any map or bitmap with an empty span, where index 0 may not
+// exist).  Same order of tests as filter_keep.
+enum { FB_NONE = 0, FB_TBM = 1, FB_EQ = 2, FB_FN = 3 };
+__device__ __forceinline__ int filter_batch_mode(const fparams &P) {
+    if (P.use_typeof) return (P.tbm && P.type_n) ? FB_TBM : FB_NONE;
+    if (P.probe_mode == PM_EQ) return FB_EQ;
+    if (P.probe_mode == PM_LIST) return FB_NONE;
+    return (P.fn_pg && P.fn_vals && P.fn_n) ? FB_FN : FB_NONE;
+}
+
+// filter_keep on the tile's K rows at once, op-major like chain_eval_batch
+// (DESIGN.md §3 item 3): all row values (and col2 values), then all bitmap
+// words or map pages, then all map values, each level's K loads issued
+// before any is consumed.  rr[] are VALID rows (a row past the end is
+// clamped by the caller and has its bit clear in `in`); a row whose value
+// is outside the span reads index 0 and is dropped.  Bit k of the result =
+// filter_keep(P, rr[k]) for the rows of `in`.  `mode` is wave-uniform.
+template <int K>
+__device__ __forceinline__ uint32_t filter_keep_batch(const fparams &P,
+                                                      int mode,
+                                                      const int64_t (&rr)[K],
+                                                      uint32_t in) {
+    uint32_t keep = in;
+    sid_t v[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) v[j] = P.tbl[rr[j] * P.ncols + P.col];
+    if (mode == FB_TBM) {
+        uint64_t ix[K], w[K];
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const uint64_t x = (uint64_t)v[j] - P.type_base;
+            const bool ok = x < P.type_n;
+            keep = ok ? keep : keep & ~(1u << j);
+            ix[j] = ok ? x : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++) w[j] = P.tbm[ix[j] >> 6];
+#pragma unroll
+        for (int j = 0; j < K; j++)
+            keep = ((w[j] >> (ix[j] & 63)) & 1) ? keep : keep & ~(1u << j);
+    } else if (mode == FB_EQ) {
+#pragma unroll
+        for (int j = 0; j < K; j++)
+            keep = (v[j] == P.cval) ? keep : keep & ~(1u << j);
+    } else {  // FB_FN: fn[a] != 0 && fn[a] == b
+        sid_t b[K];
+        if (P.probe_mode == PM_CONST) {
+#pragma unroll
+            for (int j = 0; j < K; j++) b[j] = P.cval;
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; j++)
+                b[j] = P.tbl[rr[j] * P.ncols + P.col2];
+        }
+        uint64_t ix[K], bits[K];
+        uint32_t rk[K];
+        sid_t tv[K];
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            // fn_swap: the REVERSED direction is functional
+            const sid_t a = P.fn_swap ? b[j] : v[j];
+            b[j] = P.fn_swap ? v[j] : b[j];
+            const uint64_t x = (uint64_t)a - P.fn_base;
+            const bool ok = x < P.fn_n;
+            keep = ok ? keep : keep & ~(1u << j);
+            ix[j] = ok ? x : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++) {  // one 16-B load per page
+            const uint4 q =
+                *reinterpret_cast<const uint4 *>(&P.fn_pg[ix[j] >> 6]);
+            bits[j] = (uint64_t)q.x | ((uint64_t)q.y << 32);
+            rk[j] = q.z;
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const uint64_t bit = 1ull << (ix[j] & 63);
+            const bool hit = ((keep >> j) & 1) && (bits[j] & bit);
+            keep = hit ? keep : keep & ~(1u << j);
+            // AND mask, not a select: a select lets the optimiser sink the
+            // rank word's load into the `hit` branch, behind its own wait
+            rk[j] = (rk[j] + (uint32_t)__popcll(bits[j] & (bit - 1))) &
+                    (0u - (uint32_t)hit);
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++) tv[j] = P.fn_vals[rk[j]];
+#pragma unroll
+        for (int j = 0; j < K; j++)
+            keep = (tv[j] && tv[j] == b[j]) ? keep : keep & ~(1u << j);
+    }
+    return keep;
+}
+
 __device__ __forceinline__ uint64_t filter_bytes_per_row(const fparams &P) {
     return (P.use_typeof ? 6
             : P.fn_pg ? 24
@@ -80,7 +176,10 @@ __device__ __forceinline__ uint64_t filter_bytes_per_row(const fparams &P) {
 // measured SLOWER at suite keep-rates — extra passes cost more than
 // the atomics they save.)  Row order is engine-internal; parity is
 // set-level (sparql.hpp:455-476 semantics).
-__global__ void k_filter_tpr(fparams P, int verify_only,
+// `batch`: evaluate the tile's K rows op-major (filter_keep_batch) on the
+// paths that are plain gathers; 0 (WK_FILTER_BATCH=0) or any other path:
+// row after row through filter_keep.
+__global__ void k_filter_tpr(fparams P, int verify_only, int batch,
                              uint64_t *__restrict__ d_state,
                              uint64_t *__restrict__ d_stats,
                              sid_t *__restrict__ out_tbl)
@@ -97,15 +196,33 @@ __global__ void k_filter_tpr(fparams P, int verify_only,
     const sid_t *__restrict__ tbl = P.tbl;
     const int64_t tile = (int64_t)blockDim.x * K;
     const int64_t stride = (int64_t)gridDim.x * tile;
+    const int mode = batch ? filter_batch_mode(P) : FB_NONE;  // wave-uniform
 
     for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows; base += stride) {
         bool keep[K];
         int64_t rr[K];
+        if (mode != FB_NONE) {
+            uint32_t in = 0;
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-            const int64_t r = base + k * SCAN_T + threadIdx.x;
-            rr[k] = r;
-            keep[k] = r < nrows && filter_keep(P, r);
+            for (int k = 0; k < K; k++) {
+                const int64_t r = base + k * SCAN_T + threadIdx.x;
+                in |= r < nrows ? 1u << k : 0u;
+                rr[k] = r < nrows ? r : base;  // base < nrows: a valid row
+            }
+            const uint32_t m = filter_keep_batch<K>(P, mode, rr, in);
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                keep[k] = (m >> k) & 1;
+                // a clamped row is never kept; past nrows for verify_only
+                rr[k] = ((in >> k) & 1) ? rr[k] : nrows;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const int64_t r = base + k * SCAN_T + threadIdx.x;
+                rr[k] = r;
+                keep[k] = r < nrows && filter_keep(P, r);
+            }
         }
         if (verify_only) {
             // identity-verified filter (captured graphs): the warm pass
