@@ -423,6 +423,38 @@ static bool chain_narrow(int out_cols) {
     const char *v = getenv("WK_CHAIN_WIDTH");
     return out_cols <= ROW_NARROW && !(v && atoi(v) == ROW_MAX);
 }
+// WK_CHAIN_SCHED=0: one chain op per round in plan order and no wave
+// early-out, i.e. the plain op loop through the same kernels (A/B arm of
+// the round schedule).  Read per call, like WK_CHAIN.
+static bool wk_chain_sched() {
+    const char *v = getenv("WK_CHAIN_SCHED");
+    return !(v && !atoi(v));
+}
+// Grid of the three batched chain kernels: grid_for's, but never more
+// blocks than are resident at once at the kernel's compiled occupancy
+// (queried once per instantiation), so that the grid-stride loops run as
+// one batch; every instantiation at 8 waves per SIMD keeps 2048.
+// WK_CHAIN_GRID=<n> caps it further, so that a test table of a few
+// thousand rows makes one block walk several tiles / iterations.  Read
+// per call, like WK_MIN_CAP.
+template <auto Kern>
+static int chain_grid(int64_t work) {
+    static const int resident = [] {
+        int nb = 0, dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                  dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kern, BLOCK,
+                                                         0) != hipSuccess ||
+            nb < 1 || cus < 1)
+            return 2048;
+        return std::min(2048, nb * cus);
+    }();
+    int g = std::min(grid_for(work), resident);
+    const char *v = getenv("WK_CHAIN_GRID");
+    const int cap = v ? atoi(v) : 0;
+    return cap > 0 && cap < g ? cap : g;
+}
 // WK_FILTER_BATCH=0: k_filter_tpr evaluates its rows one after another
 // (filter_keep) on every path.  Read per call, like WK_CHAIN.
 static bool wk_filter_batch() {
@@ -1176,6 +1208,7 @@ static void collect_chain(const wk_engine *e, int from,
                           std::vector<int32_t> v2c, int ncols,
                           chain_plan &cp) {
     const wk_store *st = e->st;
+    const int nc_in = ncols;
     cp.C.fn_base = st->fn_base;
     cp.C.fn_n = st->fn_n;
     cp.C.t_base = st->type_base;
@@ -1194,7 +1227,7 @@ static void collect_chain(const wk_engine *e, int from,
         const int a = col_of(pt.subject);
         if (a < 0 || p < 1) break;
         if ((sid_t)p == TYPE_ID && dir == DIR_IN) break;  // PK_INDEX
-        chain_op op{nullptr, nullptr, 0, a, 0, 0};
+        chain_op op{nullptr, nullptr, 0, a, 0, 0, -1};
         const sid_t *vals = nullptr;
         if (pt.object >= 0) {
             if ((sid_t)p == TYPE_ID && dir == DIR_OUT) {
@@ -1239,6 +1272,19 @@ static void collect_chain(const wk_engine *e, int from,
     }
     cp.C.nops = cp.npat;
     cp.out_cols = ncols;
+    // dependency rounds and the appends' destination columns
+    chain_sched_op sop[CHAIN_MAX];
+    for (int i = 0; i < cp.npat; i++)
+        sop[i] = {cp.C.op[i].kind, cp.C.op[i].a, cp.C.op[i].b};
+    chain_sched S;
+    chain_schedule(sop, cp.npat, nc_in, wk_chain_sched(), S);
+    cp.C.nrounds = S.nrounds;
+    cp.C.early_out = S.early_out;
+    for (int i = 0; i < CHAIN_MAX; i++) {
+        cp.C.op[i].dst = S.dst[i];
+        for (int s2 = 0; s2 < CHAIN_SLOTS; s2++)
+            cp.C.slot[i][s2] = S.slot[i][s2];
+    }
 }
 
 // bind a chain's appended variables to the columns from `first_col` on
@@ -1887,7 +1933,8 @@ static void launch_k2u_chain(wk_engine *e, const step_ctx &c,
     const wk_store *st = e->st;
     launch_gather_scan(e, G, /*timed*/ true, [&] {
         hipLaunchKernelGGL(
-            (k_csr_gather_chain<NC, W>), dim3(grid_for(e->bound)),
+            (k_csr_gather_chain<NC, W>),
+            dim3(chain_grid<k_csr_gather_chain<NC, W>>(e->bound)),
             dim3(BLOCK), 0, e->stream, c.cur_tbl, c.col, c_pg,
             e->gs->d_csr_entries[(size_t)c.p * 2 + c.dir], st->fn_base,
             st->fn_n, e->d_edges, cp.C, e->d_state, e->d_stats,
@@ -1896,7 +1943,8 @@ static void launch_k2u_chain(wk_engine *e, const step_ctx &c,
     });
     TIME_BEGIN(e);
     hipLaunchKernelGGL(
-        (k_expand_chain<NC, W>), dim3(grid_for(e->bound)), dim3(BLOCK), 0,
+        (k_expand_chain<NC, W>),
+        dim3(chain_grid<k_expand_chain<NC, W>>(e->bound)), dim3(BLOCK), 0,
         e->stream, c.cur_tbl, e->d_edges, (uint64_t *)e->eoff.p,
         (uint32_t *)e->cnt.p, (uint32_t *)e->pmask.p,
         (uint64_t *)e->prefix.p,
@@ -1943,7 +1991,8 @@ static int32_t step_k2u_chain(wk_engine *e, const step_ctx &c,
 template <int NC, int W>
 static void launch_row_chain(wk_engine *e, const step_ctx &c,
                              const chain_plan &cp) {
-    hipLaunchKernelGGL((k_row_chain<NC, W>), dim3(grid_for(e->bound)),
+    hipLaunchKernelGGL((k_row_chain<NC, W>),
+                       dim3(chain_grid<k_row_chain<NC, W>>(e->bound)),
                        dim3(BLOCK), 0, e->stream, c.cur_tbl, cp.C,
                        cp.out_cols, e->d_state, (uint64_t)e->cap_rows,
                        e->d_stats, c.out_tbl);

@@ -1,6 +1,7 @@
 // wk_kernels_common.h — device-side state words, probe and membership helpers shared by every kernel family.
 // Included by gpu_engine.hip only (one translation unit).
 #pragma once
+#include "wk_chain_sched.h"
 
 // ---------------------------------------------------------------------
 // device kernels
@@ -88,11 +89,7 @@ __device__ __forceinline__ bool typeof_nodrop_ok(
 // map, bitmap, column and constant, and normalised a reversed-map k2k to
 // (key col, value col).
 // ---------------------------------------------------------------------
-enum { CH_FN_APPEND = 0,  // v = fn[row[a]]; 0 drops, else append v
-       CH_TYPE = 1,       // bitmap bit of row[a] (exact, multi-type incl.)
-       CH_FN_EQ = 2,      // fn[row[a]] != 0 && == row[b]   (k2k)
-       CH_EQ = 3 };       // row[a] == cval                 (PM_EQ k2c)
-constexpr int CHAIN_MAX = 8;  // ops per chain
+// (the op kinds, CHAIN_MAX and CHAIN_SLOTS live in wk_chain_sched.h)
 constexpr int ROW_MAX = 8;    // wk_engine_begin_query rejects nvars > 8
 // narrow width bucket of the batched chain kernels: candidates of a plan
 // whose out_cols <= ROW_NARROW are carried as sid_t[ROW_NARROW]
@@ -107,11 +104,17 @@ struct chain_op {
     const void *data;    // FN_*: packed values; TYPE: membership bitmap
     int32_t kind, a, b;
     sid_t cval;
+    int32_t dst;         // FN_APPEND: the column it writes (plan order)
 };
+// op[] is in plan order (chain_eval walks it as it is); slot[r][s] is the
+// op of slot s of dependency round r, -1 = empty (chain_schedule,
+// wk_chain_sched.h), which is what chain_eval_batch walks.
 struct chain_t {
     chain_op op[CHAIN_MAX];
     uint64_t fn_base, fn_n, t_base, t_n;
-    int32_t nops;
+    int32_t nops, nrounds;
+    int32_t early_out;   // batch: a wave with no live candidate stops
+    int32_t slot[CHAIN_MAX][CHAIN_SLOTS];
 };
 
 // Column access by a (wave-uniform) runtime index as select chains: a
@@ -173,108 +176,190 @@ __device__ __forceinline__ sid_t row_pick(const sid_t (&row)[W], int c) {
     return v;
 }
 
-// Op-major evaluation of the chain on K candidate rows at once (DESIGN.md
-// §3 5i): for every op the K loads of one level (bitmap words; map pages;
-// map values) are issued before any of them is consumed, so a thread keeps
-// K independent lookups in flight where chain_eval has one.  Nothing exits
-// early: bit j of the returned mask says whether candidate j is kept (only
-// bits set in `active` can stay set), and a candidate that is inactive or
-// has failed sends its remaining loads to index 0 of the page / value /
-// bitmap array, which exists whenever the op does — the loads are
-// unconditional and the results of dropped candidates are ignored.  An op
-// whose array is null or whose span is empty reads nothing and drops every
-// candidate.  Keep/drop and the appended columns are exactly chain_eval's.
+// Evaluation of the chain on K candidate rows at once, in dependency
+// rounds.  The host schedule (chain_schedule) packs ops
+// that do not read each other's appended column into rounds of up to
+// CHAIN_SLOTS = 2 slots.  A slot is, by what it loads, SL_NONE (empty, EQ,
+// or skipped: no load), SL_BITS (TYPE: a bitmap word) or SL_MAP (FN_*: a
+// 16-B map page, then a value).  chain_round<M0, M1> is ONE round as
+// straight-line code for one pair of slot classes, in three phases over
+// both slots:
+//   A  pick the K keys, issue the K first-level loads of each slot
+//   B  BITS: test the bits.  MAP: test the page bits, rank, issue the K
+//      value loads
+//   C  MAP: FN_EQ compares, FN_APPEND writes column dst
+// so every first-level load of a round is issued before any is consumed,
+// and so is every value load: a thread has up to 2 x K independent lookups
+// in flight and a chain costs two dependent load rounds per ROUND, not per
+// op.  There is no branch between a round's loads and their use (a branch
+// there makes the compiler copy loaded registers where the arms meet, and
+// wait for the loads to do it); chain_eval_batch picks the body with one
+// wave-uniform switch per round, slots ordered by class.  The round loop
+// stays rolled, slot parameters are scalar loads from the kernel arguments
+// by a wave-uniform index.
+// Bit j of the returned mask says whether candidate j is kept (only bits
+// set in `active` can stay set).  A candidate that is inactive or has
+// failed (in an earlier round, phase or slot) sends its remaining loads to
+// index 0 of the page / value / bitmap array, which exists whenever the op
+// does — the loads are unconditional per lane and the results of dropped
+// candidates are ignored.  An op whose array is null or whose span is
+// empty reads nothing and drops every candidate.  Keep/drop and the
+// appended columns of kept candidates are exactly chain_eval's.  With
+// C.early_out a wave in which no lane has a live candidate leaves the
+// round loop (wave-uniform; the caller's barriers are outside).
 // APPEND_ONLY: the candidates are known to pass (the count pass said so);
-// only the FN_APPEND lookups are repeated, the filter ops are skipped.
+// only the FN_APPEND lookups are repeated: filter slots are skipped, the
+// rounds are kept, nothing exits early.
 // W is the candidates' compile-time width: the host picks the bucket that
 // holds the plan's out_cols (chain_width), so every column an op reads or
 // appends is below W, and the picks and sets cost W selects, not ROW_MAX.
-template <int NC, int K, bool APPEND_ONLY = false, int W = ROW_MAX>
-__device__ __forceinline__ uint32_t chain_eval_batch(
-    const chain_t &C, sid_t (&rows)[K][W], uint32_t active) {
-    static_assert(K >= 1 && K <= 32, "keep mask is 32 bits");
-    static_assert(NC <= W && W <= ROW_MAX, "the input columns must fit");
-    uint32_t keep = active;
-    int nc = NC;
-    // the op loop stays rolled: one op's parameters are read from the
-    // kernel arguments by a wave-uniform index (scalar loads), which keeps
-    // the K-wide body within the register budget
-#pragma unroll 1
-    for (int i = 0; i < C.nops; i++) {
-        const chain_op &o = C.op[i];
-        if (o.kind == CH_TYPE) {
-            if (APPEND_ONLY) continue;
+enum { SL_NONE = 0, SL_BITS = 1, SL_MAP = 2 };
+
+// phase A of one slot: keys (0 for a dead candidate) and first-level loads
+template <int M, int K, int W>
+__device__ __forceinline__ void chain_slot_load(
+    const chain_t &C, const chain_op &o, const sid_t (&rows)[K][W],
+    uint32_t &keep, uint32_t (&ix)[K], uint64_t (&bits)[K],
+    uint32_t (&rk)[K]) {
+    if constexpr (M != SL_NONE) {
+        const uint64_t base = M == SL_BITS ? C.t_base : C.fn_base;
+        const uint64_t n = M == SL_BITS ? C.t_n : C.fn_n;
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const uint64_t x = (uint64_t)row_pick(rows[j], o.a) - base;
+            const bool ok = ((keep >> j) & 1) && x < n;
+            keep = ok ? keep : keep & ~(1u << j);
+            ix[j] = ok ? (uint32_t)x : 0u;  // x < n: fits 32 bits
+        }
+        if constexpr (M == SL_BITS) {
             const uint64_t *tbm = (const uint64_t *)o.data;
-            if (!tbm || !C.t_n) { keep = 0; continue; }
-            uint64_t ix[K], w[K];
 #pragma unroll
-            for (int j = 0; j < K; j++) {
-                const uint64_t x = (uint64_t)row_pick(rows[j], o.a) - C.t_base;
-                const bool ok = ((keep >> j) & 1) && x < C.t_n;
-                keep = ok ? keep : keep & ~(1u << j);
-                ix[j] = ok ? x : 0;
-            }
-#pragma unroll
-            for (int j = 0; j < K; j++) w[j] = tbm[ix[j] >> 6];
-#pragma unroll
-            for (int j = 0; j < K; j++)
-                keep = ((w[j] >> (ix[j] & 63)) & 1) ? keep : keep & ~(1u << j);
-        } else if (o.kind == CH_EQ) {
-            if (APPEND_ONLY) continue;
-#pragma unroll
-            for (int j = 0; j < K; j++)
-                keep = (row_pick(rows[j], o.a) == o.cval) ? keep
-                                                          : keep & ~(1u << j);
+            for (int j = 0; j < K; j++) bits[j] = tbm[ix[j] >> 6];
         } else {
-            if (APPEND_ONLY && o.kind != CH_FN_APPEND) continue;
-            const sid_t *vals = (const sid_t *)o.data;
-            if (!o.pg || !vals || !C.fn_n) {
-                keep = 0;
-                if (o.kind == CH_FN_APPEND) nc++;
-                continue;
-            }
-            uint64_t ix[K], bits[K];
-            uint32_t rk[K];
-            sid_t tv[K];
 #pragma unroll
-            for (int j = 0; j < K; j++) {
-                const uint64_t x = (uint64_t)row_pick(rows[j], o.a) - C.fn_base;
-                const bool ok = ((keep >> j) & 1) && x < C.fn_n;
-                keep = ok ? keep : keep & ~(1u << j);
-                ix[j] = ok ? x : 0;
-            }
-#pragma unroll
-            for (int j = 0; j < K; j++) {  // one 16-B load per page
+            for (int j = 0; j < K; j++) {  // one 16-B page, 12 B of it used
                 const uint4 q =
                     *reinterpret_cast<const uint4 *>(&o.pg[ix[j] >> 6]);
                 bits[j] = (uint64_t)q.x | ((uint64_t)q.y << 32);
                 rk[j] = q.z;
             }
+        }
+    }
+}
+// phase B: bit tests; a map slot ranks and issues its value loads (the
+// value replaces the rank in rk)
+template <int M, int K>
+__device__ __forceinline__ void chain_slot_mid(
+    const chain_op &o, uint32_t &keep, const uint32_t (&ix)[K],
+    const uint64_t (&bits)[K], uint32_t (&rk)[K]) {
+    if constexpr (M == SL_BITS) {
 #pragma unroll
-            for (int j = 0; j < K; j++) {
-                const uint64_t bit = 1ull << (ix[j] & 63);
-                const bool hit = ((keep >> j) & 1) && (bits[j] & bit);
-                keep = hit ? keep : keep & ~(1u << j);
-                rk[j] = hit ? rk[j] + (uint32_t)__popcll(bits[j] & (bit - 1))
-                            : 0u;
-            }
+        for (int j = 0; j < K; j++)
+            keep = ((bits[j] >> (ix[j] & 63)) & 1) ? keep : keep & ~(1u << j);
+    } else if constexpr (M == SL_MAP) {
+        const sid_t *vals = (const sid_t *)o.data;
 #pragma unroll
-            for (int j = 0; j < K; j++) tv[j] = vals[rk[j]];
-            if (o.kind == CH_FN_EQ) {
+        for (int j = 0; j < K; j++) {
+            const uint64_t bit = 1ull << (ix[j] & 63);
+            const bool hit = ((keep >> j) & 1) && (bits[j] & bit);
+            keep = hit ? keep : keep & ~(1u << j);
+            rk[j] = hit ? rk[j] + (uint32_t)__popcll(bits[j] & (bit - 1)) : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++) rk[j] = vals[rk[j]];
+    }
+}
+// phase C of a map slot, without a branch: FN_EQ compares with column b
+// and sets no column (-1), FN_APPEND sets column dst
+template <int M, int K, int W>
+__device__ __forceinline__ void chain_slot_end(const chain_op &o,
+                                               sid_t (&rows)[K][W],
+                                               uint32_t &keep,
+                                               const uint32_t (&tv)[K]) {
+    if constexpr (M == SL_MAP) {
+        const bool eq = o.kind == CH_FN_EQ;
+        const int dst = eq ? -1 : o.dst;
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const bool ok = tv[j] && (!eq || tv[j] == row_pick(rows[j], o.b));
+            keep = ok ? keep : keep & ~(1u << j);
+            row_set(rows[j], dst, tv[j]);
+        }
+    }
+}
+template <int M0, int M1, int K, int W>
+__device__ __forceinline__ uint32_t chain_round(const chain_t &C,
+                                                const chain_op &o0,
+                                                const chain_op &o1,
+                                                sid_t (&rows)[K][W],
+                                                uint32_t keep) {
+    uint32_t ix0[K], ix1[K], rk0[K], rk1[K];
+    uint64_t b0[K], b1[K];
+    chain_slot_load<M0>(C, o0, rows, keep, ix0, b0, rk0);
+    chain_slot_load<M1>(C, o1, rows, keep, ix1, b1, rk1);
+    chain_slot_mid<M0>(o0, keep, ix0, b0, rk0);
+    chain_slot_mid<M1>(o1, keep, ix1, b1, rk1);
+    chain_slot_end<M0>(o0, rows, keep, rk0);
+    chain_slot_end<M1>(o1, rows, keep, rk1);
+    return keep;
+}
+
+template <int NC, int K, bool APPEND_ONLY = false, int W = ROW_MAX>
+__device__ __forceinline__ uint32_t chain_eval_batch(
+    const chain_t &C, sid_t (&rows)[K][W], uint32_t active) {
+    static_assert(K >= 1 && K <= 32, "keep mask is 32 bits");
+    static_assert(NC <= W && W <= ROW_MAX, "the input columns must fit");
+    static_assert(CHAIN_SLOTS == 2, "chain_round takes two slots");
+    uint32_t keep = active;
+#pragma unroll 1
+    for (int r = 0; r < C.nrounds; r++) {
+        // the slots' load classes (wave-uniform scalars); an EQ is decided
+        // here, an op without its array drops everything
+        int idx[2], cls[2];
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const int i = C.slot[r][s];
+            idx[s] = i < 0 ? 0 : i;
+            const chain_op &o = C.op[idx[s]];
+            cls[s] = SL_NONE;
+            if (i < 0 || (APPEND_ONLY && o.kind != CH_FN_APPEND)) continue;
+            if (o.kind == CH_EQ) {
 #pragma unroll
                 for (int j = 0; j < K; j++)
-                    keep = (tv[j] && tv[j] == row_pick(rows[j], o.b))
+                    keep = (row_pick(rows[j], o.a) == o.cval)
                                ? keep
                                : keep & ~(1u << j);
+            } else if (o.kind == CH_TYPE) {
+                if (o.data && C.t_n) cls[s] = SL_BITS;
+                else keep = 0;
             } else {
-#pragma unroll
-                for (int j = 0; j < K; j++) {
-                    keep = tv[j] ? keep : keep & ~(1u << j);
-                    row_set(rows[j], nc, tv[j]);
-                }
-                nc++;
+                if (o.pg && o.data && C.fn_n) cls[s] = SL_MAP;
+                else keep = 0;
             }
         }
+        const bool sw = cls[0] < cls[1];  // the heavier class first
+        const chain_op &o0 = C.op[sw ? idx[1] : idx[0]];
+        const chain_op &o1 = C.op[sw ? idx[0] : idx[1]];
+        switch ((sw ? cls[1] : cls[0]) * 3 + (sw ? cls[0] : cls[1])) {
+        case SL_MAP * 3 + SL_MAP:
+            keep = chain_round<SL_MAP, SL_MAP>(C, o0, o1, rows, keep);
+            break;
+        case SL_MAP * 3 + SL_BITS:
+            keep = chain_round<SL_MAP, SL_BITS>(C, o0, o1, rows, keep);
+            break;
+        case SL_MAP * 3 + SL_NONE:
+            keep = chain_round<SL_MAP, SL_NONE>(C, o0, o1, rows, keep);
+            break;
+        case SL_BITS * 3 + SL_BITS:
+            keep = chain_round<SL_BITS, SL_BITS>(C, o0, o1, rows, keep);
+            break;
+        case SL_BITS * 3 + SL_NONE:
+            keep = chain_round<SL_BITS, SL_NONE>(C, o0, o1, rows, keep);
+            break;
+        default:
+            break;
+        }
+        if (!APPEND_ONLY && C.early_out && __ballot(keep != 0) == 0) break;
     }
     return keep;
 }

@@ -528,8 +528,13 @@ __global__ void k_expand_chain_big(const sid_t *__restrict__ tbl,
 // compacted at the widened width with k_filter_tpr's ballot ranks (one
 // LDS atomic per wave, one S_TOTAL atomic per 1024-row tile); k_commit
 // follows.  Exact; nothing counts into S_DONE.
+// (1- and 2-column tables of the narrow bucket are held to the 64 VGPRs of
+// 8 waves per SIMD, at which the 2048-block grid is resident at once: the
+// two-slot round body comes out at 66 without the bound, at 64 and no
+// scratch with it; wider inputs would spill VGPRs under it and stay at 7)
 template <int NC, int W>
-__global__ void __launch_bounds__(SCAN_T)
+__global__ void
+__launch_bounds__(SCAN_T, W == ROW_NARROW && NC <= 2 ? 8 : 1)
 k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
             uint64_t *__restrict__ d_state, uint64_t cap,
             uint64_t *__restrict__ d_stats, sid_t *__restrict__ out)
