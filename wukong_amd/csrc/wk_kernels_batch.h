@@ -112,7 +112,7 @@ __global__ void k_light2(const sid_t *__restrict__ edges, uint64_t list_off,
         d_state[S_NROWS] = cnt;
         d_state[S_ERR] = 0;
         for (int i = 0; i < S_WORDS; i++) h_pin[i] = d_state[i];
-        for (int i = 0; i < CAT_COUNT; i++) h_pin[8 + i] = d_stats[i];
+        for (int i = 0; i < CAT_COUNT; i++) h_pin[HP_STATS + i] = d_stats[i];
         atomicAdd((unsigned long long *)&d_stats[CAT_FILTER],
                   (unsigned long long)(sz * 6 + cnt * 4));
     }

@@ -25,6 +25,14 @@ enum { S_NROWS = 0, S_TOTAL = 1, S_ERR = 2, S_REQ = 3, S_OVF = 4,
        S_DONE = 5, S_INROWS = 6, S_WORDS = 7 };
 enum { CAT_PROBE = 0, CAT_SCAN, CAT_EXPAND, CAT_FILTER, CAT_COPY, CAT_SPLIT,
        CAT_OTHER, CAT_COUNT };
+// pinned block (h_pin) slots: [0..S_WORDS) the published d_state words,
+// then the sticky error of the pipelined replay window (set by every
+// publish that saw S_ERR, cleared by the host alone), the CAT_COUNT byte
+// counters, and what the final publish writes (k_fin_publish)
+enum { HP_STICKY_ERR = 7, HP_STATS = 8, HP_FIN_COUNT = 16, HP_FIN_LIVE = 24 };
+static_assert(HP_STICKY_ERR >= S_WORDS, "sticky slot overlaps the state words");
+static_assert(HP_STATS + CAT_COUNT <= HP_FIN_COUNT,
+              "byte counters overlap the final-ops slots");
 
 constexpr int SCAN_T = 256;  // scan tile = block size of the fused kernels
 

@@ -887,11 +887,11 @@ __device__ __forceinline__ void publish_state(uint64_t *__restrict__ d_state,
         d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
     }
     for (int i = 0; i < S_WORDS; i++) h_pin[i] = d_state[i];
-    for (int i = 0; i < CAT_COUNT; i++) h_pin[8 + i] = d_stats[i];
-    // sticky error flag (h_pin slot 7): survives across back-to-back
-    // graph replays whose own begin kernels clear d_state — the
-    // one-sync-per-pass path checks and clears it host-side
-    if (d_state[S_ERR]) h_pin[7] = 1;
+    for (int i = 0; i < CAT_COUNT; i++) h_pin[HP_STATS + i] = d_stats[i];
+    // sticky error flag: survives across back-to-back graph replays
+    // whose own begin kernels clear d_state — the one-sync-per-pass path
+    // checks and clears it host-side
+    if (d_state[S_ERR]) h_pin[HP_STICKY_ERR] = 1;
 }
 __global__ void k_publish_state(uint64_t *__restrict__ d_state,
                                 const uint64_t *__restrict__ d_stats,

@@ -30,8 +30,8 @@
 
 // d_fin words: [0..7] per-column live-bit masks, [8] post-final row count
 enum { F_LIVE = 0, F_COUNT = 8, F_WORDS = 16 };
-// pinned slots (h_pin) the final publish writes
-enum { HP_FIN_COUNT = 16, HP_FIN_LIVE = 24 };
+// (the pinned slots the final publish writes, HP_FIN_COUNT and
+// HP_FIN_LIVE, are named with the others in wk_kernels_common.h)
 constexpr int FIN_MAXB = 1024;   // blocks of the histogram/scatter grid
 constexpr int FIN_SCAN_T = 1024; // threads of the one scan block
 
