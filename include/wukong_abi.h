@@ -177,7 +177,15 @@ void         wk_engine_destroy(wk_engine_t *);
 
 /* Enqueue a whole plan as one asynchronous launch chain (no sync) —
  * pipelined multi-engine execution = the reference proxy's in-flight
- * window (core/proxy.hpp:477-525).  Harvest with wk_engine_fetch_*. */
+ * window (core/proxy.hpp:477-525).  Harvest with wk_engine_fetch_*.
+ * A plan with UNION branches and / or an OPTIONAL group is part of the
+ * same chain (main BGP, UNION, OPTIONAL, then the FILTER conjuncts on
+ * group-born variables): the branch tables are merged on the device and
+ * nothing syncs.  An overflow anywhere in it comes back from the fetch as
+ * WK_ERR_CAP (-5) with the capacities grown: submit again.  WK_ERR_PLAN
+ * (-3) for such a plan only when WK_DEV_GROUPS=0, which leaves groups to
+ * wk_engine_run_query's host-merge path, or when two UNION branches end
+ * with different variable->column layouts. */
 int32_t wk_engine_submit(wk_engine_t *, const wk_plan_t *);
 
 /* Batched light-query window: one asynchronous launch executes n
@@ -219,7 +227,10 @@ int32_t wk_engine_light_batch_wait(wk_engine_t *, uint64_t *counts,
  * final pass.  run still returns the blind (pre-final) count;
  * wk_engine_final_count reads the post-final one, and
  * wk_engine_fetch_result of the same plan downloads the table the replay
- * already finalized.  Otherwise such a plan is WK_ERR_PLAN (-3). */
+ * already finalized.  Otherwise such a plan is WK_ERR_PLAN (-3).
+ * UNION / OPTIONAL plans are captured like any other (run returns the
+ * blind count of the merged table); WK_ERR_PLAN for them only under
+ * WK_DEV_GROUPS=0 or for a UNION branch layout mismatch. */
 int32_t wk_engine_graph_build(wk_engine_t *, const wk_plan_t *,
                               int32_t *graph_id);
 int32_t wk_engine_graph_run(wk_engine_t *, int32_t graph_id,
@@ -229,7 +240,8 @@ int32_t wk_engine_graph_run(wk_engine_t *, int32_t graph_id,
  * the reference proxy's in-flight window applied to replays. */
 /* Whole-suite capture: N plans into ONE instantiated graph (pays the
  * graph-replay floor once per pass).  Same gid space; replay with
- * wk_engine_graph_launch + wk_engine_sync. */
+ * wk_engine_graph_launch + wk_engine_sync.  Takes the plans
+ * wk_engine_graph_build takes, UNION / OPTIONAL plans included. */
 int32_t wk_engine_graph_build_suite(wk_engine_t *, const wk_plan_t *plans,
                                     int32_t nplans, int32_t *gid);
 int32_t wk_engine_graph_launch(wk_engine_t *, int32_t graph_id);

@@ -467,7 +467,12 @@ class Engine:
                 "wk_engine_create failed (no MI355X visible, or HBM alloc failed)")
 
     def submit(self, plan):
-        """Enqueue a whole plan asynchronously (harvest with fetch_*)."""
+        """Enqueue a whole plan asynchronously (harvest with fetch_*).
+        UNION branches and an OPTIONAL group are part of the chain: no
+        sync, the branches are merged on the device.  A fetch that raises
+        rc=-5 has grown the capacities: submit again.  WK_DEV_GROUPS=0
+        refuses such plans (rc=-3); run_query then takes its host-merge
+        path."""
         cplan = plan.to_c()
         rc = _eng_submit(self._h, ctypes.byref(cplan))
         if rc != 0:
@@ -484,7 +489,8 @@ class Engine:
         warm pass first); returns a graph id for graph_run.  A plan with
         distinct/limit/offset ends its chain with the device final pass
         (refused with WK_DEV_FINAL=0, for blind plans and for more than 8
-        required vars: rc=-3)."""
+        required vars: rc=-3).  Plans with UNION / OPTIONAL groups are
+        captured too (rc=-3 under WK_DEV_GROUPS=0)."""
         cplan = plan.to_c()
         gid = c_i32()
         rc = _eng_graph_build(self._h, ctypes.byref(cplan), ctypes.byref(gid))
@@ -509,7 +515,8 @@ class Engine:
     def graph_build_suite(self, plans):
         """Capture ALL plans back-to-back into ONE hipGraph (pays the
         replay floor once per pass); returns a graph id for
-        graph_launch."""
+        graph_launch.  Takes the plans graph_build takes, UNION /
+        OPTIONAL plans included."""
         cplans = (WkPlan * len(plans))()
         keep = []
         for i, p in enumerate(plans):

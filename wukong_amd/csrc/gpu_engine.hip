@@ -103,11 +103,18 @@
  *                       in one compaction; k_fin_window — the window
  *                       alone (replaces the host final_process,
  *                       sparql.hpp:1424-1551; captured into graphs)
+ *  wk_kernels_group.h
+ *   k_grp_copy/append/restart — UNION on the device: parent snapshot,
+ *                       branch append (16 B per lane, clamped to the
+ *                       capacity) and the 1-thread restart between
+ *                       branches (replaces the host merge of the branch
+ *                       tables, rmap.hpp:57-87)
  *  host side (the wk_engine_*.h headers, included below in dependency
  *  order; the first lines of each say what it holds: core, store, launch,
- *  steps, filter, final, batch, graph).  This file keeps engine create /
- *  destroy, begin_query, wk_engine_submit, UNION, OPTIONAL,
- *  wk_engine_run_query and the small utility exports.
+ *  steps, filter, final, batch, graph, group).  This file keeps engine
+ *  create / destroy, begin_query, run_plan (main BGP, UNION, OPTIONAL,
+ *  trailing FILTER: one chain), wk_engine_submit, wk_engine_run_query and
+ *  the small utility exports.
  *   zero-copy i2u/c2u — the 1-col start table IS the stored edge list
  *                       (read-only view, no copy kernel)
  *   hipGraph replay   — wk_engine_graph_build/run/launch: a fixed plan
@@ -137,6 +144,7 @@ using namespace wk;
 #include "wk_kernels_filter.h"
 #include "wk_kernels_batch.h"
 #include "wk_kernels_final.h"
+#include "wk_kernels_group.h"
 
 #include "wk_engine_core.h"
 #include "wk_engine_store.h"
@@ -146,6 +154,7 @@ using namespace wk;
 #include "wk_engine_final.h"
 #include "wk_engine_batch.h"
 #include "wk_engine_graph.h"
+#include "wk_engine_group.h"
 
 extern "C" wk_engine_t *wk_engine_create_on(wk_gpu_store_t *g) {
     if (!g) return nullptr;
@@ -159,15 +168,17 @@ extern "C" wk_engine_t *wk_engine_create_on(wk_gpu_store_t *g) {
     e->d_edges = g->d_edges;
     e->d_type_of = g->d_type_of;
     if (hipStreamCreate(&e->stream) != hipSuccess) { delete e; return nullptr; }
-    if (hipMalloc(&e->d_state, (S_WORDS + CAT_COUNT + 2) * 8) != hipSuccess ||
+    const size_t state_bytes = (S_WORDS + CAT_COUNT + 2 + G_WORDS) * 8;
+    if (hipMalloc(&e->d_state, state_bytes) != hipSuccess ||
         hipHostMalloc(&e->h_pin, 64 * sizeof(uint64_t)) != hipSuccess) {
         wk_engine_destroy(e);
         return nullptr;
     }
     e->d_stats = e->d_state + S_WORDS;
+    e->d_grp = e->d_state + S_WORDS + CAT_COUNT + 2;
     if (hipMalloc(&e->d_fin, F_WORDS * 8) != hipSuccess ||
         hipMemset(e->d_fin, 0, F_WORDS * 8) != hipSuccess ||
-        hipMemset(e->d_state, 0, (S_WORDS + CAT_COUNT + 2) * 8) != hipSuccess) {
+        hipMemset(e->d_state, 0, state_bytes) != hipSuccess) {
         wk_engine_destroy(e);
         return nullptr;
     }
@@ -194,6 +205,7 @@ extern "C" void wk_engine_destroy(wk_engine_t *e) {
     e->bsums.release(); e->misc.release(); e->ovf.release();
     e->fhist.release();
     e->oflag[0].release(); e->oflag[1].release();
+    e->gsnap.release(); e->gmerge.release();
     for (auto &g : e->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     e->lbd.release(); e->lbcnt.release();
@@ -288,14 +300,53 @@ static int32_t run_whole_plan(wk_engine *e) {
     return WK_OK;
 }
 
+// The whole plan as one launch chain, with no host sync anywhere: main BGP,
+// then UNION, then OPTIONAL (the reference's order, execute_sparql_query,
+// sparql.hpp:1564-1662), then the FILTER conjuncts on UNION-/OPTIONAL-born
+// variables (its stage 4, sparql.hpp:1651-1655).  Shared by
+// wk_engine_submit (captures included) and wk_engine_run_query.
+static int32_t run_plan(wk_engine *e, const wk_plan_t *plan) {
+    int32_t rc = plan_has_groups(plan) ? prepare_groups(e, plan) : WK_OK;
+    if (rc) return rc;
+    rc = run_whole_plan(e);
+    if (rc) return rc;
+    if (plan->nunion > 0 && plan->union_pats && plan->union_sizes) {
+        rc = run_union_dev(e, plan);
+        if (rc) return rc;
+    }
+    if (plan->nopt > 0 && plan->opt_patterns) {
+        rc = run_optional(e, plan, /*host_sync*/ false);
+        if (rc) return rc;
+    }
+    if (!e->conj.empty()) rc = apply_filters(e, -1, -1, nullptr);
+    return rc;
+}
+
+// WK_DEV_GROUPS=0: the groups with their host round trips (run_query only)
+static int32_t run_plan_host_groups(wk_engine *e, const wk_plan_t *plan) {
+    int32_t rc = run_whole_plan(e);
+    if (rc) return rc;
+    if (plan->nunion > 0 && plan->union_pats && plan->union_sizes) {
+        rc = run_union_host(e, plan);
+        if (rc) return rc;
+    }
+    if (plan->nopt > 0 && plan->opt_patterns) {
+        rc = run_optional(e, plan, /*host_sync*/ true);
+        if (rc) return rc;
+    }
+    if (!e->conj.empty()) rc = apply_filters(e, -1, -1, nullptr);
+    return rc;
+}
+
 // asynchronous whole-plan submission: enqueue the full launch chain and
 // return without any sync (pipelined multi-engine execution — the
 // reference proxy's in-flight window, proxy.hpp:477-525)
 extern "C" int32_t wk_engine_submit(wk_engine_t *e, const wk_plan_t *plan) {
     if (!e || !plan) return WK_ERR_STATE;
-    if (plan->nopt > 0 || plan->nunion > 0)
-        return WK_ERR_PLAN;  // UNION/OPTIONAL need the sync run_query path
-    const bool light = light2_eligible(e, plan);
+    const bool groups = plan->nopt > 0 || plan->nunion > 0;
+    if (groups && !wk_dev_groups())
+        return WK_ERR_PLAN;  // the host-merge path is run_query's alone
+    const bool light = !groups && light2_eligible(e, plan);
     int32_t rc = light ? begin_light(e, plan) : wk_engine_begin_query(e, plan);
     if (rc) return rc;
     if (light) {
@@ -320,97 +371,7 @@ extern "C" int32_t wk_engine_submit(wk_engine_t *e, const wk_plan_t *plan) {
         e->step = 2;
         return WK_OK;
     }
-    return run_whole_plan(e);
-}
-
-// UNION branches (sparql.hpp:1593-1614 + rmap.hpp:57-87): each branch
-// continues from the main group's result table; the final table is the
-// row-concat of the branch results.  All branches must end with the
-// same variable->column layout.
-static int32_t run_union(wk_engine *e, const wk_plan_t *plan) {
-    int32_t rc = sync_state(e);
-    if (rc) return rc;
-    const int64_t pr = e->nrows;  // == bound: sync_state just set both
-    const table_pos parent = save_pos(e);
-    const int pc = parent.ncols;
-    devbuf snap;  // freed by its destructor on every way out
-    size_t bytes = (size_t)pr * std::max(pc, 1) * 4;
-    if (bytes && pc) {
-        if (snap.ensure(bytes)) return WK_ERR_HIP;
-        // cur_table: the parent may be a zero-copy i2u view; the
-        // restore below rematerialises it into the owned buffer
-        HIP_CHECK(hipMemcpyAsync(snap.p, cur_table(e), bytes,
-                                 hipMemcpyDeviceToDevice, e->stream));
-    }
-    std::vector<sid_t> merged;
-    std::vector<int32_t> bv2c;
-    int bc = -1;
-    const wk_pattern_t *bp = plan->union_pats;
-    for (int b = 0; b < plan->nunion; b++) {
-        if (b) {  // restore the parent state for the next branch
-            restore_pos(e, parent);
-            e->tbl_view = nullptr;  // snap restore materialises the view
-            if (bytes && pc)
-                HIP_CHECK(hipMemcpyAsync(e->tbl[parent.cur].p, snap.p, bytes,
-                                         hipMemcpyDeviceToDevice, e->stream));
-            hipLaunchKernelGGL(k_set_state, dim3(1), dim3(1), 0, e->stream,
-                               e->d_state, (uint64_t)pr);
-            e->nrows = pr;
-        }
-        e->pats.assign(bp, bp + plan->union_sizes[b]);
-        e->step = 0;
-        bp += plan->union_sizes[b];
-        while (e->step < (int)e->pats.size()) {
-            rc = exec_pattern(e);
-            if (rc) return rc;
-        }
-        rc = sync_state_grow(e);
-        if (rc) return rc;
-        if (bc < 0) {
-            bc = e->ncols;
-            bv2c = e->v2c;
-        } else if (bc != e->ncols || bv2c != e->v2c) {
-            return WK_ERR_PLAN;
-        }
-        size_t off = merged.size();
-        merged.resize(off + (size_t)e->nrows * bc);
-        if (e->nrows)
-            HIP_CHECK(hipMemcpy(merged.data() + off, cur_table(e),
-                                (size_t)e->nrows * bc * 4,
-                                hipMemcpyDeviceToHost));
-    }
-    int64_t mrows = bc > 0 ? (int64_t)(merged.size() / bc) : 0;
-    rc = wk_engine_load_rbuf(e, merged.empty() ? nullptr : merged.data(),
-                             mrows, bc, bv2c.data(), 0);
-    if (rc) return rc;
-    HIP_CHECK(stream_sync(e->stream));  // merged[] is about to go away
-    return WK_OK;
-}
-
-// OPTIONAL pattern group (sparql.hpp:1616-1649, BGP-only): rows are
-// kept; unmatched rows carry BLANK_ID in the columns first bound inside
-// the group.
-static int32_t run_optional(wk_engine *e, const wk_plan_t *plan) {
-    int32_t rc = sync_state(e);
-    if (rc) return rc;
-    if (e->oflag[0].ensure((size_t)e->cap_rows) ||
-        e->oflag[1].ensure((size_t)e->cap_rows))
-        return WK_ERR_HIP;
-    HIP_CHECK(hipMemsetAsync(e->oflag[0].p, 1, (size_t)e->cap_rows,
-                             e->stream));
-    HIP_CHECK(hipMemsetAsync(e->oflag[1].p, 1, (size_t)e->cap_rows,
-                             e->stream));
-    scoped_set<int> opt_mode(e->opt_mode, 1);
-    e->ocur = 0;
-    e->opt_mask = 0;
-    e->pats.assign(plan->opt_patterns, plan->opt_patterns + plan->nopt);
-    e->step = 0;
-    while (e->step < (int)e->pats.size()) {
-        rc = exec_pattern(e);
-        if (!rc) rc = sync_state_grow(e);
-        if (rc) return rc;
-    }
-    return WK_OK;
+    return run_plan(e, plan);
 }
 
 extern "C" int32_t wk_engine_run_query(wk_engine_t *e, const wk_plan_t *plan,
@@ -418,26 +379,9 @@ extern "C" int32_t wk_engine_run_query(wk_engine_t *e, const wk_plan_t *plan,
     for (int attempt = 0; attempt < 6; attempt++) {
         int32_t rc = wk_engine_begin_query(e, plan);
         if (rc) return rc;
-        rc = run_whole_plan(e);
+        rc = wk_dev_groups() ? run_plan(e, plan) : run_plan_host_groups(e, plan);
+        if (rc == WK_ERR_CAP) continue;  // a host-merge sync saw the overflow
         if (rc) return rc;
-        // UNION then OPTIONAL, the reference's order
-        // (execute_sparql_query, sparql.hpp:1564-1662)
-        if (plan->nunion > 0 && plan->union_pats && plan->union_sizes) {
-            rc = run_union(e, plan);
-            if (rc == WK_ERR_CAP) continue;
-            if (rc) return rc;
-        }
-        if (plan->nopt > 0 && plan->opt_patterns) {
-            rc = run_optional(e, plan);
-            if (rc == WK_ERR_CAP) continue;
-            if (rc) return rc;
-        }
-        // FILTER conjuncts on UNION-/OPTIONAL-born variables: the
-        // reference's stage 4 (sparql.hpp:1651-1655)
-        if (!e->conj.empty()) {
-            rc = apply_filters(e, -1, -1, nullptr);
-            if (rc) return rc;
-        }
         rc = wk_engine_fetch_result(e, plan, out);
         if (rc != WK_ERR_CAP) return rc;
         // overflow: fetch grew the caps; re-run the whole query

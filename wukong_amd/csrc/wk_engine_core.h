@@ -43,8 +43,8 @@ struct devbuf {
     devbuf() = default;
     devbuf(const devbuf &) = delete;
     devbuf &operator=(const devbuf &) = delete;
-    ~devbuf() { release(); }  // locals (e.g. run_union's snapshot) free
-                              // on every early-return path
+    ~devbuf() { release(); }  // locals (e.g. run_union_host's snapshot)
+                              // free on every early-return path
     int ensure(size_t bytes) {
         if (bytes <= cap) return WK_OK;
         if (p) (void)hipFree(p);
@@ -142,6 +142,7 @@ struct wk_engine {
 
     uint64_t *d_state = nullptr;  // S_WORDS words
     uint64_t *d_stats = nullptr;  // CAT_COUNT words (algorithmic bytes)
+    uint64_t *d_grp = nullptr;    // G_WORDS words (UNION group state)
     uint64_t *d_fin = nullptr;    // F_WORDS words (final-ops state)
     uint64_t *h_pin = nullptr;    // pinned: state + stats snapshot
     void *h_stage = nullptr;      // pinned staging for result downloads
@@ -193,7 +194,19 @@ struct wk_engine {
     bool fin_table = false;
     fin_sig_t fin_sig;
 
-    // OPTIONAL group execution state (wk_engine_run_query only)
+    // UNION on the device: the parent-table snapshot the
+    // branches restart from and the merged table they append to.  Sized
+    // like tbl[] (cap_rows x cap_cols words), grow-only, allocated by the
+    // first UNION plan (ensure_group_bufs) and grown with tbl[] from then
+    // on (grow_caps), so no capture ever allocates.
+    devbuf gsnap, gmerge;
+    bool grp_bufs = false;
+    // inside a UNION branch or the OPTIONAL group: e->pats is the group's
+    // pattern list and e->step indexes it, so the per-main-pattern capture
+    // hints do not apply (hint_nodrop)
+    bool in_group = false;
+
+    // OPTIONAL group execution state (every whole-plan entry point)
     devbuf oflag[2];          // per-row matched flags (u8), ping-pong
     int opt_mode = 0;         // inside an OPTIONAL pattern group
     int ocur = 0;             // which oflag is current
@@ -263,7 +276,10 @@ static inline const sid_t *cur_table(wk_engine *e) {
 // any in-place writer, e.g. the OPTIONAL-group BLANK fill)
 static int32_t materialize_view(wk_engine *e) {
     if (!e->tbl_view) return WK_OK;
-    size_t bytes = (size_t)std::max<int64_t>(e->nrows, 0) *
+    // sized by the host bound: exact for a view into the store (step_start
+    // sets it to the list length) and never more than the buffer holds;
+    // e->nrows is valid only after a sync, which this path does not have
+    size_t bytes = (size_t)std::max<int64_t>(e->bound, 0) *
                    std::max(e->ncols, 1) * 4;
     if (bytes &&
         hipMemcpyAsync(e->tbl[e->cur].p, e->tbl_view, bytes,
@@ -340,6 +356,10 @@ static bool wk_dev_final() { return knob_on("WK_DEV_FINAL"); }
 // 0 = suite captures keep k_publish_state + k_begin_state as two launches
 // between queries
 static bool wk_fuse_pair() { return knob_on("WK_FUSE_PAIR"); }
+// 0 = UNION / OPTIONAL plans only through wk_engine_run_query, with the
+// host merge of the branches and a sync per group pattern; submit and the
+// graph builders refuse them
+static bool wk_dev_groups() { return knob_on("WK_DEV_GROUPS"); }
 // default 8192: a non-captured fetch of fewer rows keeps the host final
 // ops — below that the ~30-launch device chain costs more than the host
 // sort.  0 = always the device.  Captured graphs always end
@@ -462,6 +482,9 @@ static int32_t grow_caps(wk_engine *e, int64_t rows, int cols) {
     if (e->ovf.ensure((size_t)(rows + 1) * 4)) return WK_ERR_HIP;
     if (e->bsums.ensure(2056 * 8)) return WK_ERR_HIP;
     if (e->fhist.ensure((size_t)fin_grid(rows) * 256 * 4)) return WK_ERR_HIP;
+    if (e->grp_bufs && (e->gsnap.ensure((size_t)rows * cols * 4) ||
+                        e->gmerge.ensure((size_t)rows * cols * 4)))
+        return WK_ERR_HIP;
     e->cap_rows = rows;
     e->cap_cols = cols;
     return WK_OK;

@@ -146,6 +146,11 @@ struct capture_scope {
 // guard still sees every query; S_ERR on replay = capacity overflow or a
 // failed hint: the caller falls back to the plain submit path.
 //
+// A plan with a UNION or an OPTIONAL group is one chain like any other
+// (run_plan; refused under WK_DEV_GROUPS=0).  Its main BGP is never
+// truncated, and inside the groups no warm-pass hint applies: the hints
+// are indexed by main-BGP pattern (hint_nodrop).
+//
 // A plan with final ops ends its chain with the device final pass.
 // Replay returns the BLIND row count (pre-DISTINCT/LIMIT) and
 // wk_engine_final_count reads the final one, so without the device pass
@@ -164,11 +169,17 @@ static int32_t capture_plans(wk_engine *e, const wk_plan_t *plans, int n,
     std::vector<int> empty_after((size_t)n, -1);
     for (int i = 0; i < n; i++) {
         const wk_plan_t *plan = &plans[i];
-        if (plan->nopt > 0 || plan->nunion > 0) return WK_ERR_PLAN;
+        const bool groups = plan->nopt > 0 || plan->nunion > 0;
+        if (groups && !wk_dev_groups()) return WK_ERR_PLAN;
         if (plan_has_final(plan) && (plan->blind || !wk_dev_final()))
             return WK_ERR_PLAN;
         int32_t rc = graph_warm_hints(e, plan, hints[i], &empty_after[i]);
         if (rc) return rc;
+        // A group plan keeps its whole main BGP: the publish guards a
+        // truncated tail by expecting an EMPTY final table, and a UNION
+        // branch that opens with a constant or index start replaces the
+        // empty parent with rows of its own.
+        if (groups) empty_after[i] = -1;
     }
     hipGraph_t g = nullptr;
     int32_t rc = WK_OK;

@@ -29,9 +29,12 @@ static void with_ncols(int ncols, F &&f) {
 // ---- pieces shared by the step_* operators ---------------------------
 
 // warm-pass hint: pattern `step` dropped no rows (consulted ONLY while
-// capturing a graph)
+// capturing a graph).  The hints are indexed by MAIN-BGP pattern: inside a
+// UNION branch or the OPTIONAL group e->step counts the group's patterns
+// and no hint applies.
 static bool hint_nodrop(const wk_engine *e, int step) {
-    return e->capturing && step < (int)e->capture_hint.size() &&
+    return e->capturing && !e->in_group &&
+           step < (int)e->capture_hint.size() &&
            e->capture_hint[step];
 }
 
