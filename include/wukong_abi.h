@@ -207,8 +207,14 @@ int32_t wk_engine_submit_light_batch(wk_engine_t *, const int64_t *subj,
  * emulator's multi-pattern templates A4/A6.  consts[i] replaces
  * patterns[0].subject.  Blind replies only; a query whose table
  * outgrows LDS reports count UINT64_MAX and must be re-run on the
- * per-pattern path.  WK_ERR_PLAN = template shape not interpretable, or
- * the template carries a FILTER (the interpreter evaluates none). */
+ * per-pattern path.  WK_ERR_PLAN = the caller falls back to the
+ * per-pattern path; nothing a template carries is silently dropped.
+ * Refused: a FILTER, DISTINCT, limit >= 0, offset > 0, an OPTIONAL
+ * group, UNION branches; more than 8 patterns or variables; a first
+ * pattern that is not `const predicate ?var` (index start, predicate
+ * variable, an object outside -1..-nvars); a later pattern with a
+ * constant subject, a predicate variable, a subject variable that
+ * nothing bound, or a new variable that would be the 9th column. */
 int32_t wk_engine_submit_plan_batch(wk_engine_t *, const wk_plan_t *tmpl,
                                     const int64_t *consts, int32_t n);
 /* Blocks until the window completes; fills the n per-query row counts

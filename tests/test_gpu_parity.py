@@ -218,8 +218,10 @@ def test_emulator_templates_parity(lubm4, store4, oracle4):
 def test_light_batch_parity(store4, oracle4):
     """Batched light-query window (wk_engine_submit_light_batch — one
     launch per window, one wavefront workgroup per query) vs per-query
-    oracle counts, including empty-pool constants and double-buffered
-    back-to-back windows."""
+    oracle counts, including a nonexistent constant: three windows of
+    different sizes, one after the other on one engine, each harvested
+    before the next is submitted.  Windows in flight on several engines
+    at once are test_gpu_plan_batch_edges.py's."""
     import random
     eng = wk.Engine(store4, device=0)
     rng = random.Random(11)

@@ -587,8 +587,12 @@ class Engine:
         self._cplan_batch = cplan  # keepalive for pattern array
 
     def wait_light_batch(self):
-        """Block until the window completes; per-query row counts."""
-        n = self._lb_n
+        """Block until the window completes; per-query row counts.
+        RuntimeError when no window is in flight (a refused submit
+        leaves none)."""
+        n = getattr(self, "_lb_n", None)
+        if n is None:
+            raise RuntimeError("light_batch_wait: no window in flight")
         counts = np.empty(n, dtype=np.uint64)
         rc = _eng_lb_wait(self._h, counts.ctypes.data_as(ctypes.POINTER(c_u64)), n)
         if rc != 0:

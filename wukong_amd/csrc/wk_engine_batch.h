@@ -84,12 +84,17 @@ extern "C" int32_t wk_engine_submit_light_batch(wk_engine_t *e,
 
 // Compile a light whole-plan template for the LDS interpreter; the
 // per-query constant replaces patterns[0].subject.  WK_ERR_PLAN = shape
-// not interpretable (caller uses the per-pattern path instead).
+// not interpretable (caller uses the per-pattern path instead).  The
+// interpreter runs the main patterns and nothing else, so whatever else
+// a plan can carry is refused here, never dropped: DISTINCT, LIMIT,
+// OFFSET, an OPTIONAL group, UNION branches (FILTER: the entry point).
 static int32_t compile_light_plan(const wk_engine *e, const wk_plan_t *plan,
                                   lplan_t *lp) {
     if (!plan || plan->npatterns < 1 || plan->npatterns > 8) return WK_ERR_PLAN;
     if (plan->nvars < 1 || plan->nvars > 8) return WK_ERR_PLAN;
-    if (plan->distinct || plan->limit >= 0) return WK_ERR_PLAN;
+    if (plan->distinct || plan->limit >= 0 || plan->offset > 0)
+        return WK_ERR_PLAN;
+    if (plan->nopt > 0 || plan->nunion > 0) return WK_ERR_PLAN;
     const wk_store *st = e->st;
     int32_t v2c[8];
     for (int i = 0; i < 8; i++) v2c[i] = -1;
@@ -98,6 +103,7 @@ static int32_t compile_light_plan(const wk_engine *e, const wk_plan_t *plan,
     if (p0.subject < 0 || is_tpid(p0.subject) || p0.object >= 0 ||
         p0.predicate < 0)
         return WK_ERR_PLAN;  // must be const_to_unknown, fixed predicate
+    if (-(p0.object + 1) >= plan->nvars) return WK_ERR_PLAN;
     const wk::seg_t *seg = st->seg_of(1ull << NBITS_IDX,
                                       (uint64_t)p0.predicate, p0.direction);
     lp->ops[0] = {LOP_C2U, 0, 0, p0.direction, 0, (uint32_t)p0.predicate,
