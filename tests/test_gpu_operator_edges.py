@@ -538,6 +538,29 @@ def test_capacity_truncation():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("store", ["default", "hash"])
+def test_capacity_ends_inside_a_queued_row(ctx, engines, store):
+    """WK_MIN_CAP=16 on the three- and four-row start sets of the P_DEG
+    plans: the first row fits, the capacity ends inside the next one (33
+    edges of T_N1, 34 of T_OD: the one-wave-per-row pass clamps at
+    `pos < cap`) and the rows behind it start past the capacity.  On the
+    default store that is the type-fused writer pair (k_expand_tf /
+    k_expand_tf_big), on the hash store k_probe_scan + k_expand_in /
+    k_expand_big.  The first fetch reports the overflow; the re-run at
+    the grown capacity is exact."""
+    with env(WK_MIN_CAP=16, **STORE_ENVS[store]):
+        for name in ("deg-nodrop", "deg-onedrop"):
+            plan, want = PLANS[name], ctx.want(name, PLANS[name])
+            assert len(want) > 16 + 33
+            eng = wk.Engine(engines[store]._store, device=0)
+            eng.submit(plan)
+            assert eng.fetch_count() < 0, name
+            got = eng.run_query(plan)
+            assert got.shape == want.shape, (name, got.shape, want.shape)
+            assert np.array_equal(sort_rows(got), want), name
+
+
+@pytest.mark.gpu
 def test_plan_batch_capacity_boundary(ctx, engines):
     """LDS plan interpreter at LP_CAP: a c2u list of LP_CAP - 1 and
     LP_CAP edges fits, LP_CAP + 1 overflows; a c2u -> k2u table of

@@ -20,10 +20,33 @@
  * those of a single file:
  *  wk_kernels_common.h
  *   probe_one/probe_chain, bsearch_u32, tbm_has, csr_entry,
- *   typeof_nodrop_ok — lookup helpers; d_state words and categories;
+ *   type_of_dense, typeof_check, typeof_nodrop_ok — lookup helpers;
+ *   d_state words and categories, commit_rows and begin_state — what one
+ *   thread writes at a step's end / a query's begin; tile_compact — the
+ *   ballot-rank compaction of the one-pass filters and k_row_chain;
  *   chain_eval (row-major, early exit) and chain_eval_batch (op-major,
  *   K candidates of compile-time width W, no early exit) — the per-row
  *   op chain evaluators
+ *  wk_kernels_state.h
+ *   k_commit, k_set_state, k_begin_state, k_zero_words,
+ *   k_publish_state, k_publish_begin, k_project — 1-thread state
+ *                       kernels, projection.
+ *                       A query's begin zeroing rides on its first state
+ *                       write (k_begin_state); the optimistic kernels
+ *                       count guard misses into the sticky S_DONE word,
+ *                       which k_publish_state alone turns into S_ERR —
+ *                       no per-step commit for steps that keep the row
+ *                       count
+ *  wk_kernels_scan.h
+ *   wave_incl_scan, block_excl_scan, block_ladder_scan — scan helpers;
+ *   scan_pos, ovf_push, wave_emit_rows — what the writers behind the
+ *   scan share
+ *   k_scan_local/mid  — chunked exclusive scan with DEVICE-side length
+ *                       (replaces the thrust scans, gpu_hash.cu:587-596):
+ *                       several elements per thread, wave scan, one
+ *                       barrier per tile; k_scan_mid also commits the
+ *                       step (S_INROWS snapshot for the scatter side);
+ *                       k_scan_*_ladder are their WK_SCAN=0 siblings
  *  wk_kernels_expand.h
  *   k_probe_scan      — fused gen-keys + thread-per-row cluster-hash
  *                       probe + in-kernel prefix scan (2-deep bucket
@@ -49,26 +72,12 @@
  *                       are instantiated <NC, W>: candidate rows are 4
  *                       columns wide when the plan's widened row fits,
  *                       else 8; WK_CHAIN_WIDTH=8 forces 8)
- *   k_scan_local/mid  — chunked exclusive scan with DEVICE-side length
- *                       (replaces the thrust scans, gpu_hash.cu:587-596):
- *                       several elements per thread, wave scan, one
- *                       barrier per tile; k_scan_mid also commits the
- *                       step (S_INROWS snapshot for the scatter side)
  *   k_expand_in/big   — input-centric expansion + wave-per-big-row pass
  *                       (replaces gpu_hash.cu:762-834; no 20-col cap),
  *                       optional inline no-drop typeof verify in graphs
  *   k_fn_gather/k_fn_scatter — functional-predicate rank-compressed
  *                       map k2u (deg==1 segments; page+value gathers);
  *                       k_expand_fn_map = optimistic 1:1 inside graphs
- *   k_commit, k_set_state, k_begin_state, k_zero_words,
- *   k_publish_state, k_publish_begin, k_project — 1-thread state
- *                       kernels, projection.
- *                       A query's begin zeroing rides on its first state
- *                       write (k_begin_state); the optimistic kernels
- *                       count guard misses into the sticky S_DONE word,
- *                       which k_publish_state alone turns into S_ERR —
- *                       no per-step commit for steps that keep the row
- *                       count
  *  wk_kernels_filter.h
  *   k_filter_tpr      — fused probe/typeof filter + block compaction
  *                       (replaces gpu_hash.cu:326-445,523-585);
@@ -140,6 +149,8 @@
 using namespace wk;
 
 #include "wk_kernels_common.h"
+#include "wk_kernels_state.h"
+#include "wk_kernels_scan.h"
 #include "wk_kernels_expand.h"
 #include "wk_kernels_filter.h"
 #include "wk_kernels_batch.h"

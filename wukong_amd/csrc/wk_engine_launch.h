@@ -271,32 +271,36 @@ struct expand_verify {  // fused no-drop typeof check (captured graphs)
     int on = 0;
 };
 
-template <int NC>
-static void launch_expand_t(wk_engine *e, const sid_t *cur_tbl, sid_t *out_tbl,
-                            int G, const expand_verify &vf) {
-    hipLaunchKernelGGL(k_expand_in<NC>, dim3(grid_for(e->bound)), dim3(BLOCK), 0,
-                       e->stream, cur_tbl, e->ncols, e->d_edges,
-                       (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p,
-                       (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p, G,
-                       e->d_state, (uint64_t)e->cap_rows, e->d_stats,
-                       (uint32_t *)e->ovf.p, vf.tbm, vf.type_of, vf.base,
-                       vf.n, vf.cval, vf.on, out_tbl);
-    hipLaunchKernelGGL(k_expand_big<NC>, dim3(512), dim3(BLOCK), 0, e->stream,
-                       cur_tbl, e->ncols, e->d_edges, (uint64_t *)e->eoff.p,
-                       (uint32_t *)e->cnt.p, (uint64_t *)e->prefix.p,
-                       (uint64_t *)e->bsums.p, G, e->d_state,
-                       (uint64_t)e->cap_rows,
-                       (uint32_t *)e->ovf.p, vf.tbm, vf.type_of, vf.base,
-                       vf.n, vf.cval, vf.on, out_tbl);
+// (each launch_* below picks the kernels' compile-time column count with
+// with_ncols, whose lambda launches them directly)
+static void launch_expand(wk_engine *e, const sid_t *cur_tbl, sid_t *out_tbl,
+                          int G, const expand_verify &vf) {
+    with_ncols(e->ncols, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        hipLaunchKernelGGL(k_expand_in<NC>, dim3(grid_for(e->bound)),
+                           dim3(BLOCK), 0, e->stream, cur_tbl, e->ncols,
+                           e->d_edges, (uint64_t *)e->eoff.p,
+                           (uint32_t *)e->cnt.p, (uint64_t *)e->prefix.p,
+                           (uint64_t *)e->bsums.p, G, e->d_state,
+                           (uint64_t)e->cap_rows, e->d_stats,
+                           (uint32_t *)e->ovf.p, vf.tbm, vf.type_of, vf.base,
+                           vf.n, vf.cval, vf.on, out_tbl);
+        hipLaunchKernelGGL(k_expand_big<NC>, dim3(512), dim3(BLOCK), 0,
+                           e->stream, cur_tbl, e->ncols, e->d_edges,
+                           (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p,
+                           (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p, G,
+                           e->d_state, (uint64_t)e->cap_rows,
+                           (uint32_t *)e->ovf.p, vf.tbm, vf.type_of, vf.base,
+                           vf.n, vf.cval, vf.on, out_tbl);
+    });
     // a fused verify's misses sit in the sticky S_DONE word until the
     // publish: no epilogue launch
 }
 
-template <int NC>
-static void launch_expand_fn_t(wk_engine *e, const sid_t *cur_tbl,
-                               sid_t *out_tbl, const fnpage_t *d_pg,
-                               const sid_t *d_vals, int col,
-                               bool fuse, sid_t fcval, const seg_t *fseg) {
+static void launch_expand_fn(wk_engine *e, const sid_t *cur_tbl,
+                             sid_t *out_tbl, const fnpage_t *d_pg,
+                             const sid_t *d_vals, int col,
+                             bool fuse, sid_t fcval, const seg_t *fseg) {
     const uint64_t *tbm = fuse ? type_bitmap(e, fcval) : nullptr;
     // atomic-free pipeline: 1:1 gather of resolved objects (+0/1
     // counts), deterministic positions via the chunked scan, then a
@@ -315,72 +319,49 @@ static void launch_expand_fn_t(wk_engine *e, const sid_t *cur_tbl,
                            e->d_stats, (sid_t *)e->ovf.p,
                            (uint32_t *)e->cnt.p);
     });
-    hipLaunchKernelGGL(k_fn_scatter<NC>, dim3(grid_for(e->bound)), dim3(BLOCK),
-                       0, e->stream, cur_tbl, (const sid_t *)e->ovf.p,
-                       (const uint32_t *)e->cnt.p, (const uint64_t *)e->prefix.p,
-                       (const uint64_t *)e->bsums.p, G, e->d_state, e->d_stats,
-                       out_tbl);
-}
-
-template <int NC>
-static void launch_expand_fn_map_t(wk_engine *e, const sid_t *cur_tbl,
-                                   sid_t *out_tbl, const fnpage_t *d_pg,
-                                   const sid_t *d_vals,
-                                   int col, bool fuse, sid_t fcval) {
-    const uint64_t *tbm = fuse ? type_bitmap(e, fcval) : nullptr;
-    hipLaunchKernelGGL(k_expand_fn_map<NC>, dim3(grid_for(e->bound)),
-                       dim3(BLOCK), 0, e->stream, cur_tbl, d_pg, d_vals,
-                       e->st->fn_base, e->st->fn_n, col, fuse ? 1 : 0, tbm,
-                       e->d_type_of, e->st->type_base, e->st->type_n, fcval,
-                       e->d_state, e->d_stats, out_tbl);
+    with_ncols(e->ncols, [&](auto nc) {
+        hipLaunchKernelGGL(k_fn_scatter<decltype(nc)::value>,
+                           dim3(grid_for(e->bound)), dim3(BLOCK), 0, e->stream,
+                           cur_tbl, (const sid_t *)e->ovf.p,
+                           (const uint32_t *)e->cnt.p,
+                           (const uint64_t *)e->prefix.p,
+                           (const uint64_t *)e->bsums.p, G, e->d_state,
+                           e->d_stats, out_tbl);
+    });
 }
 
 static void launch_expand_fn_map(wk_engine *e, const sid_t *cur_tbl,
                                  sid_t *out_tbl, const fnpage_t *d_pg,
                                  const sid_t *d_vals, int col,
                                  bool fuse, sid_t fcval) {
+    const uint64_t *tbm = fuse ? type_bitmap(e, fcval) : nullptr;
     with_ncols(e->ncols, [&](auto nc) {
-        launch_expand_fn_map_t<decltype(nc)::value>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval);
+        hipLaunchKernelGGL(k_expand_fn_map<decltype(nc)::value>,
+                           dim3(grid_for(e->bound)), dim3(BLOCK), 0, e->stream,
+                           cur_tbl, d_pg, d_vals, e->st->fn_base, e->st->fn_n,
+                           col, fuse ? 1 : 0, tbm, e->d_type_of,
+                           e->st->type_base, e->st->type_n, fcval, e->d_state,
+                           e->d_stats, out_tbl);
     });
-}
-
-static void launch_expand_fn(wk_engine *e, const sid_t *cur_tbl,
-                             sid_t *out_tbl, const fnpage_t *d_pg,
-                             const sid_t *d_vals, int col,
-                             bool fuse, sid_t fcval, const seg_t *fseg) {
-    with_ncols(e->ncols, [&](auto nc) {
-        launch_expand_fn_t<decltype(nc)::value>(e, cur_tbl, out_tbl, d_pg, d_vals, col, fuse, fcval, fseg);
-    });
-}
-
-template <int NC>
-static void launch_expand_tf_t(wk_engine *e, const sid_t *cur_tbl,
-                               sid_t *out_tbl, int G, const uint64_t *tbm) {
-    hipLaunchKernelGGL(k_expand_tf<NC>, dim3(grid_for(e->bound)), dim3(BLOCK),
-                       0, e->stream, cur_tbl, e->ncols, e->d_edges,
-                       (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p,
-                       (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p, G,
-                       tbm, e->st->type_base, e->st->type_n, e->d_state,
-                       (uint64_t)e->cap_rows, e->d_stats,
-                       (uint32_t *)e->ovf.p, out_tbl);
-    hipLaunchKernelGGL(k_expand_tf_big<NC>, dim3(512), dim3(BLOCK), 0,
-                       e->stream, cur_tbl, e->ncols, e->d_edges,
-                       (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p,
-                       (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p, G,
-                       tbm, e->st->type_base, e->st->type_n, e->d_state,
-                       (uint64_t)e->cap_rows, (uint32_t *)e->ovf.p, out_tbl);
 }
 
 static void launch_expand_tf(wk_engine *e, const sid_t *cur_tbl,
                              sid_t *out_tbl, int G, const uint64_t *tbm) {
     with_ncols(e->ncols, [&](auto nc) {
-        launch_expand_tf_t<decltype(nc)::value>(e, cur_tbl, out_tbl, G, tbm);
-    });
-}
-
-static void launch_expand(wk_engine *e, const sid_t *cur_tbl, sid_t *out_tbl,
-                          int G, const expand_verify &vf) {
-    with_ncols(e->ncols, [&](auto nc) {
-        launch_expand_t<decltype(nc)::value>(e, cur_tbl, out_tbl, G, vf);
+        constexpr int NC = decltype(nc)::value;
+        hipLaunchKernelGGL(k_expand_tf<NC>, dim3(grid_for(e->bound)),
+                           dim3(BLOCK), 0, e->stream, cur_tbl, e->ncols,
+                           e->d_edges, (uint64_t *)e->eoff.p,
+                           (uint32_t *)e->cnt.p, (uint64_t *)e->prefix.p,
+                           (uint64_t *)e->bsums.p, G, tbm, e->st->type_base,
+                           e->st->type_n, e->d_state, (uint64_t)e->cap_rows,
+                           e->d_stats, (uint32_t *)e->ovf.p, out_tbl);
+        hipLaunchKernelGGL(k_expand_tf_big<NC>, dim3(512), dim3(BLOCK), 0,
+                           e->stream, cur_tbl, e->ncols, e->d_edges,
+                           (uint64_t *)e->eoff.p, (uint32_t *)e->cnt.p,
+                           (uint64_t *)e->prefix.p, (uint64_t *)e->bsums.p, G,
+                           tbm, e->st->type_base, e->st->type_n, e->d_state,
+                           (uint64_t)e->cap_rows, (uint32_t *)e->ovf.p,
+                           out_tbl);
     });
 }

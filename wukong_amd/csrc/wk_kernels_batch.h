@@ -98,8 +98,7 @@ __global__ void k_light2(const sid_t *__restrict__ edges, uint64_t list_off,
     __syncthreads();
     for (uint64_t i = threadIdx.x; i < sz; i += blockDim.x) {
         sid_t v = edges[list_off + i];
-        uint64_t idx = (uint64_t)v - type_base;
-        uint16_t t = (idx < type_n) ? type_of[idx] : 0;
+        const uint16_t t = type_of_dense(type_of, type_base, type_n, v);
         if ((sid_t)t == cval) {
             unsigned p = atomicAdd(&cnt, 1u);
             out[p] = v;
@@ -149,8 +148,7 @@ __global__ void k_light_batch(const sid_t *__restrict__ edges,
     sid_t *qout = out + d.out_off;
     for (uint64_t i = threadIdx.x; i < d.sz; i += blockDim.x) {
         sid_t v = edges[d.off + i];
-        uint64_t idx = (uint64_t)v - type_base;
-        uint16_t t = (idx < type_n) ? type_of[idx] : 0;
+        const uint16_t t = type_of_dense(type_of, type_base, type_n, v);
         if ((sid_t)t == d.cval) {
             unsigned p = atomicAdd(&cnt, 1u);
             qout[p] = v;
@@ -341,7 +339,6 @@ __global__ void k_peer_step(const wk_peer_desc *__restrict__ peers, int nsrv,
 {
     const int64_t nrows = (int64_t)d_state[S_NROWS];
     count_bytes(d_stats, CAT_PROBE, (uint64_t)nrows * (4 + 128 + 8));
-    __shared__ uint64_t sh[SCAN_T];
     const int oc = pmode == PM_SIZE ? ncols + 1 : ncols;
     uint64_t carry = 0;
     for (int64_t base = 0; base < nrows; base += SCAN_T) {
@@ -358,12 +355,10 @@ __global__ void k_peer_step(const wk_peer_desc *__restrict__ peers, int nsrv,
             // the same [v|TYPE|OUT] segment
             if (pmode == PM_CONST && pid == TYPE_ID && dir == DIR_OUT &&
                 P.type_of) {
-                uint64_t tix = (uint64_t)v - P.type_base;
-                uint16_t t = (tix < P.type_n) ? P.type_of[tix] : 0;
-                if (t != 0xFFFF) {
-                    deg = ((sid_t)t == cval) ? 1 : 0;
-                    resolved = true;
-                }
+                const int tc = typeof_check(nullptr, P.type_of, P.type_base,
+                                            P.type_n, cval, v);
+                deg = tc == TC_YES ? 1 : 0;
+                resolved = tc != TC_MULTI;
             }
             if (!resolved && seg.nb[owner]) {
                 uint64_t eoff = 0, esz = 0;
@@ -379,17 +374,9 @@ __global__ void k_peer_step(const wk_peer_desc *__restrict__ peers, int nsrv,
                 }
             }
         }
-        sh[threadIdx.x] = deg;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        uint64_t pos = carry + sh[threadIdx.x] - deg;
-        carry += sh[SCAN_T - 1];
-        __syncthreads();
+        uint64_t total;
+        const uint64_t pos = carry + block_ladder_scan(deg, &total) - deg;
+        carry += total;
         if (r < nrows && deg) {
             if (pmode == PM_SIZE) {
                 for (uint64_t k = 0; k < deg; k++) {
@@ -406,15 +393,6 @@ __global__ void k_peer_step(const wk_peer_desc *__restrict__ peers, int nsrv,
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) {  // single block: commit inline (k_commit)
-        uint64_t t = carry;
-        if (t > cap) {
-            d_state[S_ERR] = 1;
-            d_state[S_REQ] = max(d_state[S_REQ], t);
-            t = cap;
-        }
-        d_state[S_NROWS] = t;
-        d_state[S_TOTAL] = 0;
-        d_state[S_OVF] = 0;
-    }
+    if (threadIdx.x == 0)  // single block: commit inline, as k_commit would
+        commit_rows(d_state, carry, cap, /*snapshot_inrows*/ false);
 }

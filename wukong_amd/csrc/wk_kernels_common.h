@@ -1,4 +1,6 @@
-// wk_kernels_common.h — device-side state words, probe and membership helpers shared by every kernel family.
+// wk_kernels_common.h — device-side state words with the step commit and
+// query begin, probe / membership / type lookups, the tile compaction and
+// the op-chain evaluators: what every kernel family shares.
 // Included by gpu_engine.hip only (one translation unit).
 #pragma once
 #include "wk_chain_sched.h"
@@ -73,20 +75,110 @@ __device__ __forceinline__ uint64_t csr_entry(const fnpage_t *__restrict__ pg,
     return rk == RANK_MISS ? 0 : entries[rk];
 }
 
-// No-drop verify of `v rdf:type cval` inside the verify-fused expansions
-// (k_expand_in / k_expand_big): bitmap when present, else dense type_of.
-// The engine treats multi-type entities (type_of == 0xFFFF) in three
-// DELIBERATELY different ways — keep them apart:
-//   - here: a miss (-> S_DONE -> k_publish_state -> S_ERR -> safe re-run)
+// Dense side index: the single type id of v, 0 = untyped or outside
+// [base, base+n), TYPE_MULTI = several types (only a probe can tell)
+constexpr uint16_t TYPE_MULTI = 0xFFFF;
+__device__ __forceinline__ uint16_t type_of_dense(
+    const uint16_t *__restrict__ type_of, uint64_t base, uint64_t n, sid_t v) {
+    const uint64_t tix = (uint64_t)v - base;
+    return tix < n ? type_of[tix] : 0;
+}
+
+// `v rdf:type cval` without a probe: the per-type bitmap when it is built
+// (exact, multi-type included), else the dense index, which answers
+// TC_MULTI for a multi-type v.  What TC_MULTI means is each caller's own,
+// DELIBERATELY different — keep them apart:
+//   - typeof_nodrop_ok, k_expand_fn_map: a miss (-> S_DONE ->
+//     k_publish_state -> S_ERR -> safe re-run)
 //   - filter_keep: falls through to the hash probe
-//   - k_fn_gather: probes [v|TYPE|OUT]
+//   - k_fn_gather, k_peer_step: probe [v|TYPE|OUT]
+enum { TC_NO = 0, TC_YES = 1, TC_MULTI = 2 };
+__device__ __forceinline__ int typeof_check(
+    const uint64_t *__restrict__ tbm, const uint16_t *__restrict__ type_of,
+    uint64_t base, uint64_t n, sid_t cval, sid_t v) {
+    if (tbm) return tbm_has(tbm, base, n, v) ? TC_YES : TC_NO;
+    const uint16_t t = type_of_dense(type_of, base, n, v);
+    if (t == TYPE_MULTI) return TC_MULTI;
+    return (sid_t)t == cval ? TC_YES : TC_NO;
+}
+
+// No-drop verify of `v rdf:type cval` inside the optimistic kernels of a
+// captured plan (k_expand_in / k_expand_big / k_expand_fn_map)
 __device__ __forceinline__ bool typeof_nodrop_ok(
     const uint64_t *__restrict__ tbm, const uint16_t *__restrict__ type_of,
     uint64_t base, uint64_t n, sid_t cval, sid_t v) {
-    if (tbm) return tbm_has(tbm, base, n, v);
-    const uint64_t tix = (uint64_t)v - base;
-    const uint16_t t = (tix < n) ? type_of[tix] : 0;
-    return t != 0xFFFF && (sid_t)t == cval;
+    return typeof_check(tbm, type_of, base, n, cval, v) == TC_YES;
+}
+
+// Step commit: nrows = min(total, cap); an overflow raises S_ERR and the
+// required capacity for the host re-run (replaces the reference's
+// rbuf-overflow assert, gpu_engine_cuda.hpp:185).  S_TOTAL and S_OVF are
+// zeroed for the next step (saves a k_zero_words launch per step).  One
+// thread calls it.  snapshot_inrows: the commit sits BETWEEN a step's scan
+// and its writers (k_scan_mid*), which read the input row count from
+// S_INROWS; a commit behind the writers (k_commit, k_peer_step) leaves
+// S_INROWS alone.
+__device__ __forceinline__ void commit_rows(uint64_t *__restrict__ d_state,
+                                            uint64_t total, uint64_t cap,
+                                            bool snapshot_inrows) {
+    if (snapshot_inrows) d_state[S_INROWS] = d_state[S_NROWS];
+    if (total > cap) {
+        d_state[S_ERR] = 1;
+        d_state[S_REQ] = max(d_state[S_REQ], total);
+        total = cap;
+    }
+    d_state[S_NROWS] = total;
+    d_state[S_TOTAL] = 0;
+    d_state[S_OVF] = 0;
+}
+
+// query begin: zero every state word (S_ERR/S_REQ and the sticky S_DONE
+// miss word included), then set the start row count
+__device__ __forceinline__ void begin_state(uint64_t *__restrict__ d_state,
+                                            uint64_t nrows) {
+#pragma unroll
+    for (int i = 0; i < S_WORDS; i++) d_state[i] = 0;
+    d_state[S_NROWS] = nrows;
+}
+
+// lanes below `lane` whose bit is set in a ballot mask: the lane's rank
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask, int lane) {
+    return (uint32_t)__popcll(mask & ((1ull << lane) - 1));
+}
+
+// Ballot-rank compaction of one tile of SCAN_T * K rows (thread t holds
+// rows t, t + SCAN_T, ...; bit k of `keep` = its k-th row survives): K
+// ballots per thread, one LDS atomic per wave, ONE S_TOTAL atomic per
+// tile, three barriers.  Owns its three LDS words; every thread of the
+// SCAN_T-thread block calls it once per tile.  Fills mask[k] with the
+// wave's ballot of slot k and returns the output position of the wave's
+// first survivor: the survivor of slot k in lane l goes to
+//   returned base + popcount(mask[0..k-1]) + lanes_below(mask[k], l)
+// Positions are not clamped: a caller whose output can outgrow its input
+// tests pos < cap itself (k_commit flags the overflow).
+template <int K>
+__device__ __forceinline__ uint64_t tile_compact(
+    uint32_t keep, uint64_t *__restrict__ d_state, uint64_t (&mask)[K]) {
+    __shared__ unsigned long long s_base;
+    __shared__ unsigned int s_cnt;
+    __shared__ unsigned int s_wbase[SCAN_T / 64];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    uint32_t wtot = 0;
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        mask[k] = __ballot((keep >> k) & 1);
+        wtot += (uint32_t)__popcll(mask[k]);
+    }
+    if (lane == 0) s_wbase[wid] = atomicAdd(&s_cnt, wtot);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        s_base = s_cnt ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
+                                   (unsigned long long)s_cnt)
+                       : 0;
+    __syncthreads();
+    return s_base + s_wbase[wid];
 }
 
 // ---------------------------------------------------------------------

@@ -1,4 +1,6 @@
-// wk_kernels_expand.h — probe / scan / expand kernels and the 1-thread state kernels.
+// wk_kernels_expand.h — probe and gather kernels (the front half of a
+// known_to_unknown step), the writers behind the scan with their big-row
+// passes, and the stand-alone row pass k_row_chain.
 // Included by gpu_engine.hip only (one translation unit).
 #pragma once
 
@@ -23,7 +25,6 @@ __global__ void k_probe_scan(const vertex_t *__restrict__ verts,
     const int64_t chunk = (nrows + gridDim.x - 1) / gridDim.x;
     const int64_t start = (int64_t)blockIdx.x * chunk;
     const int64_t end = min(start + chunk, nrows);
-    __shared__ uint64_t sh[SCAN_T];
     uint64_t carry = 0;
 
     // 2-deep pipeline: the NEXT tile row's first bucket is issued before
@@ -90,17 +91,10 @@ __global__ void k_probe_scan(const vertex_t *__restrict__ verts,
             d_eoff[r] = eoff;
             d_cnt[r] = (uint32_t)esz;
         }
-        sh[threadIdx.x] = esz;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        if (r < end) d_pre[r] = carry + sh[threadIdx.x] - esz;
-        carry += sh[SCAN_T - 1];
-        __syncthreads();
+        uint64_t total;
+        const uint64_t incl = block_ladder_scan(esz, &total);
+        if (r < end) d_pre[r] = carry + incl - esz;
+        carry += total;
     }
     if (threadIdx.x == 0) bsums[blockIdx.x] = (start < end) ? carry : 0;
 }
@@ -193,15 +187,13 @@ __global__ void k_expand_tf(const sid_t *__restrict__ tbl, int ncols,
          r += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t keep = d_cnt[r];
         if (!keep) continue;
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        const uint64_t basep = scan_pos(d_pre, bsums, chunk, r);
         if (basep >= cap) continue;
         const uint64_t e = d_eoff[r];
         const uint64_t off = csr_off(e);
         const uint32_t len = csr_len(e);
         if (len > 32) {
-            unsigned long long i = atomicAdd(
-                (unsigned long long *)&d_state[S_OVF], 1ull);
-            ovf[i] = (uint32_t)r;
+            ovf_push(d_state, ovf, r);
             continue;
         }
         sid_t row[NC];
@@ -240,41 +232,20 @@ __global__ void k_expand_tf_big(const sid_t *__restrict__ tbl, int ncols,
     const int64_t chunk = (nrows + G - 1) / G;
     constexpr int oc = NC + 1;
     (void)ncols;
-    const int lane = threadIdx.x & 63;
     const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t q = w0; q < nq; q += nw) {
         const int64_t r = ovf[q];
         const uint64_t e = d_eoff[r];
-        const uint64_t off = csr_off(e);
-        const uint32_t len = csr_len(e);
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        const uint64_t basep = scan_pos(d_pre, bsums, chunk, r);
         if (basep >= cap) continue;
-        sid_t row[NC];
+        sid_t row[oc];
 #pragma unroll
         for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-        uint64_t wbase = 0;  // passing-rank base across 64-edge chunks
-        for (uint32_t k0 = 0; k0 < len; k0 += 64) {
-            const uint32_t k = k0 + lane;
-            bool pass = false;
-            sid_t v = 0;
-            if (k < len) {
-                v = edges[off + k];
-                pass = tbm_has(tbm, t_base, t_n, v);
-            }
-            uint64_t mask = __ballot(pass);
-            if (pass) {
-                uint64_t pos = basep + wbase +
-                               (uint64_t)__popcll(mask & ((1ull << lane) - 1));
-                if (pos < cap) {
-                    sid_t *dst = out + (int64_t)pos * oc;
-#pragma unroll
-                    for (int c = 0; c < NC; c++) dst[c] = row[c];
-                    dst[NC] = v;
-                }
-            }
-            wbase += (uint64_t)__popcll(mask);
-        }
+        wave_emit_rows<NC>(row, edges + csr_off(e), csr_len(e), basep, cap, oc,
+                           out, [&](const sid_t (&cand)[oc]) {
+                               return tbm_has(tbm, t_base, t_n, cand[NC]);
+                           });
     }
 }
 
@@ -410,15 +381,13 @@ k_expand_chain(const sid_t *__restrict__ tbl,
          r += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t keep = d_cnt[r];
         if (!keep) continue;
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        const uint64_t basep = scan_pos(d_pre, bsums, chunk, r);
         if (basep >= cap) continue;
         const uint64_t e = d_eoff[r];
         const uint64_t off = csr_off(e);
         const uint32_t len = csr_len(e);
         if (len > 32) {
-            unsigned long long i = atomicAdd(
-                (unsigned long long *)&d_state[S_OVF], 1ull);
-            ovf[i] = (uint32_t)r;
+            ovf_push(d_state, ovf, r);
             continue;
         }
         sid_t in[NC];
@@ -482,42 +451,22 @@ __global__ void k_expand_chain_big(const sid_t *__restrict__ tbl,
     const int64_t nq = (int64_t)d_state[S_OVF];
     const int64_t nrows = (int64_t)d_state[S_INROWS];
     const int64_t chunk = (nrows + G - 1) / G;
-    const int lane = threadIdx.x & 63;
     const int64_t w0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t q = w0; q < nq; q += nw) {
         const int64_t r = ovf[q];
         const uint64_t e = d_eoff[r];
-        const uint64_t off = csr_off(e);
-        const uint32_t len = csr_len(e);
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        const uint64_t basep = scan_pos(d_pre, bsums, chunk, r);
         if (basep >= cap) continue;
         sid_t row[ROW_MAX];
 #pragma unroll
         for (int c = 0; c < ROW_MAX; c++) row[c] = 0;
 #pragma unroll
         for (int c = 0; c < NC; c++) row[c] = tbl[r * NC + c];
-        uint64_t wbase = 0;  // passing-rank base across 64-edge chunks
-        for (uint32_t k0 = 0; k0 < len; k0 += 64) {
-            const uint32_t k = k0 + lane;
-            bool pass = false;
-            if (k < len) {
-                row[NC] = edges[off + k];
-                pass = chain_eval<NC + 1>(C, row);
-            }
-            uint64_t mask = __ballot(pass);
-            if (pass) {
-                uint64_t pos = basep + wbase +
-                               (uint64_t)__popcll(mask & ((1ull << lane) - 1));
-                if (pos < cap) {
-                    sid_t *dst = out + (int64_t)pos * oc;
-#pragma unroll
-                    for (int c = 0; c < ROW_MAX; c++)
-                        if (c < oc) dst[c] = row[c];
-                }
-            }
-            wbase += (uint64_t)__popcll(mask);
-        }
+        wave_emit_rows<NC>(row, edges + csr_off(e), csr_len(e), basep, cap, oc,
+                           out, [&](sid_t (&cand)[ROW_MAX]) {
+                               return chain_eval<NC + 1>(C, cand);
+                           });
     }
 }
 
@@ -525,9 +474,9 @@ __global__ void k_expand_chain_big(const sid_t *__restrict__ tbl,
 // that does not follow a CSR expansion, as ONE kernel over the table
 // (possibly a zero-copy view): each thread evaluates the chain op-major
 // on the 4 rows of its tile slots (chain_eval_batch), survivors are
-// compacted at the widened width with k_filter_tpr's ballot ranks (one
-// LDS atomic per wave, one S_TOTAL atomic per 1024-row tile); k_commit
-// follows.  Exact; nothing counts into S_DONE.
+// compacted at the widened width with tile_compact, whose positions can
+// pass the capacity here (FN_APPEND widens the rows): pos < cap is tested
+// per row; k_commit follows.  Exact; nothing counts into S_DONE.
 // (1- and 2-column tables of the narrow bucket are held to the 64 VGPRs of
 // 8 waves per SIMD, at which the 2048-block grid is resident at once: the
 // two-slot round body comes out at 66 without the bound, at 64 and no
@@ -543,11 +492,7 @@ k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
     constexpr int K = 4;
     const int64_t nrows = (int64_t)d_state[S_NROWS];
     count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * (4 * NC + 4 * oc));
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned int s_cnt;
-    __shared__ unsigned int s_wbase[SCAN_T / 64];
     const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
     const int64_t tile = (int64_t)SCAN_T * K;
     const int64_t stride = (int64_t)gridDim.x * tile;
     for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows;
@@ -566,27 +511,11 @@ k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
             for (int c = 0; c < NC; c++) rows[k][c] = tbl[rr * NC + c];
         }
         const uint32_t keep = chain_eval_batch<NC, K>(C, rows, active);
-        if (threadIdx.x == 0) s_cnt = 0;
-        __syncthreads();
         uint64_t mask[K];
-        uint32_t wtot = 0;
+        uint64_t wpos = tile_compact<K>(keep, d_state, mask);
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            mask[k] = __ballot((keep >> k) & 1);
-            wtot += (uint32_t)__popcll(mask[k]);
-        }
-        if (lane == 0) s_wbase[wid] = atomicAdd(&s_cnt, wtot);
-        __syncthreads();
-        if (threadIdx.x == 0)
-            s_base = s_cnt ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
-                                       (unsigned long long)s_cnt)
-                           : 0;
-        __syncthreads();
-        uint64_t wpos = s_base + s_wbase[wid];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const uint64_t pos =
-                wpos + (uint32_t)__popcll(mask[k] & ((1ull << lane) - 1));
+            const uint64_t pos = wpos + lanes_below(mask[k], lane);
             if (((keep >> k) & 1) && pos < cap) {  // past cap: k_commit flags
                 sid_t *dst = out + (int64_t)pos * oc;
 #pragma unroll
@@ -596,113 +525,6 @@ k_row_chain(const sid_t *__restrict__ tbl, chain_t C, int oc,
             wpos += (uint32_t)__popcll(mask[k]);
         }
     }
-}
-
-// inclusive scan of one u64 per lane across the 64-lane wave (6 cross-
-// lane steps, no LDS, no barrier)
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, int lane) {
-#pragma unroll
-    for (int ofs = 1; ofs < 64; ofs <<= 1) {
-        const uint64_t t = __shfl_up((unsigned long long)v, ofs);
-        if (lane >= ofs) v += t;
-    }
-    return v;
-}
-
-// Block-wide exclusive offset of this thread's `tsum` among the SCAN_T
-// threads, plus the block total: wave scan in registers, the SCAN_T/64
-// wave totals through LDS, ONE barrier.  s_wtot is the caller's
-// [2][SCAN_T/64] ping-pong (`par` = tile parity), which is what makes a
-// single barrier per tile enough: a wave can only reach the tile that
-// rewrites a slot after passing the barrier of the tile in between,
-// i.e. after every wave has read that slot.
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t tsum,
-                                                    uint64_t (*s_wtot)[SCAN_T / 64],
-                                                    int par, uint64_t *total) {
-    static_assert(SCAN_T == 256, "four wave totals");
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint64_t incl = wave_incl_scan(tsum, lane);
-    if (lane == 63) s_wtot[par][wid] = incl;
-    __syncthreads();
-    const uint64_t w0 = s_wtot[par][0], w1 = s_wtot[par][1],
-                   w2 = s_wtot[par][2], w3 = s_wtot[par][3];
-    const uint64_t wbase = (wid > 0 ? w0 : 0) + (wid > 1 ? w1 : 0) +
-                           (wid > 2 ? w2 : 0);
-    *total = w0 + w1 + w2 + w3;
-    return wbase + incl - tsum;
-}
-
-// chunked exclusive prefix of d_cnt -> d_pre + per-chunk sums (same
-// chunk math as k_probe_scan so the expansion kernels are unchanged).
-// Each thread owns SCAN_PER consecutive rows and sums them in registers;
-// one barrier per SCAN_T*SCAN_PER-row tile (block_excl_scan).
-constexpr int SCAN_PER = 4;
-__global__ void __launch_bounds__(SCAN_T)
-k_scan_local(const uint32_t *__restrict__ d_cnt,
-             const uint64_t *__restrict__ d_state,
-             uint64_t *__restrict__ d_pre, uint64_t *__restrict__ bsums)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    const int G = gridDim.x;
-    const int64_t chunk = (nrows + G - 1) / G;
-    const int64_t start = (int64_t)blockIdx.x * chunk;
-    const int64_t end = min(start + chunk, (int64_t)nrows);
-    __shared__ uint64_t s_wtot[2][SCAN_T / 64];
-    uint64_t carry = 0;
-    int par = 0;
-    for (int64_t base = start; base < end;
-         base += SCAN_T * SCAN_PER, par ^= 1) {
-        const int64_t r0 = base + (int64_t)threadIdx.x * SCAN_PER;
-        const uint32_t c0 = (r0 < end) ? d_cnt[r0] : 0u;
-        const uint32_t c1 = (r0 + 1 < end) ? d_cnt[r0 + 1] : 0u;
-        const uint32_t c2 = (r0 + 2 < end) ? d_cnt[r0 + 2] : 0u;
-        const uint32_t c3 = (r0 + 3 < end) ? d_cnt[r0 + 3] : 0u;
-        uint64_t total;
-        uint64_t pre = carry + block_excl_scan((uint64_t)c0 + c1 + c2 + c3,
-                                               s_wtot, par, &total);
-        if (r0 < end) d_pre[r0] = pre;
-        pre += c0;
-        if (r0 + 1 < end) d_pre[r0 + 1] = pre;
-        pre += c1;
-        if (r0 + 2 < end) d_pre[r0 + 2] = pre;
-        pre += c2;
-        if (r0 + 3 < end) d_pre[r0 + 3] = pre;
-        carry += total;
-    }
-    if (threadIdx.x == 0) bsums[blockIdx.x] = (start < end) ? carry : 0;
-}
-
-// WK_SCAN=0: the previous Hillis-Steele ladders (one element per thread
-// in LDS, ~18 barriers per SCAN_T elements), kept so the rewrite can be
-// timed alone.  Same arguments, launch shape and outputs.
-__global__ void k_scan_local_ladder(const uint32_t *__restrict__ d_cnt,
-                                    const uint64_t *__restrict__ d_state,
-                                    uint64_t *__restrict__ d_pre,
-                                    uint64_t *__restrict__ bsums)
-{
-    const int64_t nrows = (int64_t)d_state[S_NROWS];
-    const int G = gridDim.x;
-    const int64_t chunk = (nrows + G - 1) / G;
-    const int64_t start = (int64_t)blockIdx.x * chunk;
-    const int64_t end = min(start + chunk, (int64_t)nrows);
-    __shared__ uint64_t sh[SCAN_T];
-    uint64_t carry = 0;
-    for (int64_t base = start; base < end; base += SCAN_T) {
-        const int64_t r = base + threadIdx.x;
-        uint64_t esz = (r < end) ? d_cnt[r] : 0;
-        sh[threadIdx.x] = esz;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        if (r < end) d_pre[r] = carry + sh[threadIdx.x] - esz;
-        carry += sh[SCAN_T - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsums[blockIdx.x] = (start < end) ? carry : 0;
 }
 
 // fn-expansion scatter (phase 4 of gather -> scan_local -> scan_mid ->
@@ -724,193 +546,13 @@ __global__ void k_fn_scatter(const sid_t *__restrict__ tbl,
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          r < nrows; r += (int64_t)gridDim.x * blockDim.x) {
         if (!d_cnt[r]) continue;
-        uint64_t pos = d_pre[r] + bsums[r / chunk];
+        const uint64_t pos = scan_pos(d_pre, bsums, chunk, r);
         sid_t *dst = out + (int64_t)pos * oc;
         const sid_t *srow = tbl + r * NC;
 #pragma unroll
         for (int c = 0; c < NC; c++) dst[c] = srow[c];
         dst[NC] = d_val[r];
     }
-}
-
-// finish the scan across blocks: exclusive over the G block sums
-// (single block).  Fuses the step commit (k_commit semantics): the
-// pipeline total is known here, the following scatter kernels read
-// the INPUT row count from the S_INROWS snapshot, and S_OVF (the
-// big-row queue this chain is about to fill) starts clean — saving
-// the separate 1-thread commit launch per k2u/fn step.
-__device__ __forceinline__ void scan_mid_commit(uint64_t *__restrict__ d_state,
-                                                uint64_t t, uint64_t cap) {
-    d_state[S_INROWS] = d_state[S_NROWS];
-    if (t > cap) {
-        d_state[S_ERR] = 1;
-        d_state[S_REQ] = max(d_state[S_REQ], t);
-        t = cap;
-    }
-    d_state[S_NROWS] = t;
-    d_state[S_TOTAL] = 0;
-    d_state[S_OVF] = 0;
-}
-
-// Each thread owns per = ceil(G/SCAN_T) (at most SCAN_MID_PER)
-// consecutive sums in registers; one barrier per tile (block_excl_scan).
-// scan_grid caps G at SCAN_T*SCAN_MID_PER, so the tile loop runs once.
-constexpr int SCAN_MID_PER = 8;
-__global__ void __launch_bounds__(SCAN_T)
-k_scan_mid(uint64_t *__restrict__ bsums, int G, uint64_t cap,
-           uint64_t *__restrict__ d_state)
-{
-    __shared__ uint64_t s_wtot[2][SCAN_T / 64];
-    const int per = min((G + SCAN_T - 1) / SCAN_T, SCAN_MID_PER);
-    uint64_t carry = 0;
-    int par = 0;
-    for (int base = 0; base < G; base += SCAN_T * per, par ^= 1) {
-        const int i0 = base + (int)threadIdx.x * per;
-        uint64_t v[SCAN_MID_PER];  // fully unrolled: stays in registers
-        uint64_t tsum = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_MID_PER; k++) {
-            v[k] = (k < per && i0 + k < G) ? bsums[i0 + k] : 0;
-            tsum += v[k];
-        }
-        uint64_t total;
-        uint64_t pre = carry + block_excl_scan(tsum, s_wtot, par, &total);
-#pragma unroll
-        for (int k = 0; k < SCAN_MID_PER; k++) {
-            if (k < per && i0 + k < G) bsums[i0 + k] = pre;
-            pre += v[k];
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) scan_mid_commit(d_state, carry, cap);
-}
-
-// WK_SCAN=0 sibling of k_scan_mid (see k_scan_local_ladder)
-__global__ void k_scan_mid_ladder(uint64_t *__restrict__ bsums, int G,
-                                  uint64_t cap, uint64_t *__restrict__ d_state)
-{
-    __shared__ uint64_t sh[SCAN_T];
-    uint64_t carry = 0;
-    for (int base = 0; base < G; base += SCAN_T) {
-        int i = base + threadIdx.x;
-        uint64_t x = (i < G) ? bsums[i] : 0;
-        sh[threadIdx.x] = x;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t v = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += v;
-            __syncthreads();
-        }
-        if (i < G) bsums[i] = carry + sh[threadIdx.x] - x;
-        carry += sh[SCAN_T - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        d_state[S_INROWS] = d_state[S_NROWS];
-        uint64_t t = carry;
-        if (t > cap) {
-            d_state[S_ERR] = 1;
-            d_state[S_REQ] = max(d_state[S_REQ], t);
-            t = cap;
-        }
-        d_state[S_NROWS] = t;
-        d_state[S_TOTAL] = 0;
-        d_state[S_OVF] = 0;
-    }
-}
-
-// advance: nrows = min(total, cap); flag overflow for the host re-run
-// (replaces the reference's rbuf-overflow assert, gpu_engine_cuda.hpp:185).
-// Stays a 1-thread kernel: a commit fused into the last finishing block
-// of a wide producer bumps one done-word per block, which serializes at
-// ~88 atomics/us and costs more than this launch (k_peer_step, a single
-// block, commits inline).
-__global__ void k_commit(uint64_t *__restrict__ d_state, uint64_t cap) {
-    uint64_t t = d_state[S_TOTAL];
-    if (t > cap) {
-        d_state[S_ERR] = 1;
-        d_state[S_REQ] = max(d_state[S_REQ], t);
-        t = cap;
-    }
-    d_state[S_NROWS] = t;
-    // reset the accumulators for the next step (saves a 3us k_zero_words
-    // launch per step — the state kernels were 12% of suite GPU time)
-    d_state[S_TOTAL] = 0;
-    d_state[S_OVF] = 0;
-}
-
-__global__ void k_set_state(uint64_t *__restrict__ d_state, uint64_t nrows) {
-    d_state[S_NROWS] = nrows;
-    d_state[S_TOTAL] = 0;
-    d_state[S_OVF] = 0;
-}
-
-// query begin fused with the first state write: zero every state word
-// (S_ERR/S_REQ and the sticky S_DONE miss word included), then set the
-// start row count — one launch instead of k_zero_words + k_set_state
-__global__ void k_begin_state(uint64_t *__restrict__ d_state, uint64_t nrows) {
-#pragma unroll
-    for (int i = 0; i < S_WORDS; i++) d_state[i] = 0;
-    d_state[S_NROWS] = nrows;
-}
-
-// device projection to required-var columns (sparql.hpp:1510-1536)
-struct cols8 { int32_t c[8]; };
-__global__ void k_project(const sid_t *__restrict__ tbl, int ncols,
-                          const uint64_t *__restrict__ d_state, cols8 cols,
-                          int rc, sid_t *__restrict__ out)
-{
-    const int64_t n = (int64_t)d_state[S_NROWS];
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * rc;
-         t += (int64_t)gridDim.x * blockDim.x) {
-        int64_t i = t / rc;
-        int j = (int)(t - i * rc);
-        int c = cols.c[j];
-        out[t] = (c >= 0) ? tbl[i * ncols + c] : (sid_t)0xFFFFFFFFu;
-    }
-}
-
-// The optimistic kernels of a captured plan (k_expand_fn_map, the
-// verify-only k_filter_tpr, the verify-fused k_expand_in/_big) count
-// their guard misses into S_DONE, which nothing clears during a query;
-// the conversion to S_ERR happens ONCE, here, before the words are
-// copied out.  expect_empty (captured plans with a truncated empty
-// tail): the skipped patterns are only valid on an empty table, so any
-// row left raises S_ERR the same way.
-__device__ __forceinline__ void publish_state(uint64_t *__restrict__ d_state,
-                                              const uint64_t *__restrict__ d_stats,
-                                              uint64_t *__restrict__ h_pin,
-                                              int expect_empty) {
-    if (d_state[S_DONE] || (expect_empty && d_state[S_NROWS])) {
-        d_state[S_ERR] = 1;
-        d_state[S_REQ] = max(d_state[S_REQ], d_state[S_NROWS]);
-    }
-    for (int i = 0; i < S_WORDS; i++) h_pin[i] = d_state[i];
-    for (int i = 0; i < CAT_COUNT; i++) h_pin[HP_STATS + i] = d_stats[i];
-    // sticky error flag: survives across back-to-back graph replays
-    // whose own begin kernels clear d_state — the one-sync-per-pass path
-    // checks and clears it host-side
-    if (d_state[S_ERR]) h_pin[HP_STICKY_ERR] = 1;
-}
-__global__ void k_publish_state(uint64_t *__restrict__ d_state,
-                                const uint64_t *__restrict__ d_stats,
-                                uint64_t *__restrict__ h_pin,
-                                int expect_empty) {
-    publish_state(d_state, d_stats, h_pin, expect_empty);
-}
-
-// Suite captures: query i's publish followed by query i+1's begin, the
-// same writes in the same order from one thread — one launch for two
-// 
-__global__ void k_publish_begin(uint64_t *__restrict__ d_state,
-                                const uint64_t *__restrict__ d_stats,
-                                uint64_t *__restrict__ h_pin,
-                                int expect_empty, uint64_t nrows) {
-    publish_state(d_state, d_stats, h_pin, expect_empty);
-#pragma unroll
-    for (int i = 0; i < S_WORDS; i++) d_state[i] = 0;
-    d_state[S_NROWS] = nrows;
 }
 
 // Input-centric expansion (known_to_unknown back half,
@@ -950,12 +592,10 @@ __global__ void k_expand_in(const sid_t *__restrict__ tbl, int ncols,
          r += (int64_t)gridDim.x * blockDim.x) {
         uint32_t deg = d_cnt[r];
         if (!deg) continue;
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
-        if (basep >= cap) continue;  // overflow: flagged by k_commit
+        const uint64_t basep = scan_pos(d_pre, bsums, chunk, r);
+        if (basep >= cap) continue;  // overflow: flagged by k_scan_mid
         if (deg > 32) {
-            unsigned long long i = atomicAdd(
-                (unsigned long long *)&d_state[S_OVF], 1ull);
-            ovf[i] = (uint32_t)r;
+            ovf_push(d_state, ovf, r);
             continue;
         }
         if (basep + deg > cap) deg = (uint32_t)(cap - basep);
@@ -1016,7 +656,7 @@ __global__ void k_expand_big(const sid_t *__restrict__ tbl, int ncols,
     for (int64_t q = w0; q < nq; q += nw) {
         const int64_t r = ovf[q];
         uint64_t deg = d_cnt[r];
-        uint64_t basep = d_pre[r] + bsums[r / chunk];
+        const uint64_t basep = scan_pos(d_pre, bsums, chunk, r);
         if (basep >= cap) continue;
         if (basep + deg > cap) deg = cap - basep;
         sid_t row[NC];
@@ -1077,20 +717,15 @@ __global__ void k_fn_gather(const sid_t *__restrict__ tbl, int ncols,
         sid_t v = tbl[r * ncols + col];
         sid_t tv = fn_lookup(fn_pg, fn_vals, fn_base, fn_n, v);
         if (tv && use_typeof) {
-            if (tbm) {  // bitmap: decision is exact (multi-type incl.)
-                if (!tbm_has(tbm, type_base, type_n, tv)) tv = 0;
-            } else {
-                uint64_t tix = (uint64_t)tv - type_base;
-                uint16_t t = (tix < type_n) ? type_of[tix] : 0;
-                if (t != 0xFFFF) {
-                    if ((sid_t)t != fcval) tv = 0;
-                } else {
-                    uint64_t eo = 0, es = 0;
-                    probe_one(verts, f_bstart, f_nbuckets,
-                              key_pack(tv, TYPE_ID, (uint64_t)DIR_OUT), eo,
-                              es);
-                    if (!(es && bsearch_u32(edges + eo, es, fcval))) tv = 0;
-                }
+            const int tc =
+                typeof_check(tbm, type_of, type_base, type_n, fcval, tv);
+            if (tc == TC_MULTI) {
+                uint64_t eo = 0, es = 0;
+                probe_one(verts, f_bstart, f_nbuckets,
+                          key_pack(tv, TYPE_ID, (uint64_t)DIR_OUT), eo, es);
+                if (!(es && bsearch_u32(edges + eo, es, fcval))) tv = 0;
+            } else if (tc == TC_NO) {
+                tv = 0;
             }
         }
         d_val[r] = tv;
@@ -1129,16 +764,8 @@ __global__ void k_expand_fn_map(const sid_t *__restrict__ tbl,
         sid_t v = tbl[r * NC + col];
         sid_t tv = fn_lookup(fn_pg, fn_vals, fn_base, fn_n, v);
         bool ok = tv != 0;
-        if (ok && use_typeof) {
-            if (tbm) {
-                ok = tbm_has(tbm, type_base, type_n, tv);
-            } else {
-                uint64_t tix = (uint64_t)tv - type_base;
-                uint16_t t = (tix < type_n) ? type_of[tix] : 0;
-                ok = ((sid_t)t == fcval);  // 0xFFFF never matches ->
-                                           // counts as miss -> fallback
-            }
-        }
+        if (ok && use_typeof)  // multi-type counts as a miss -> fallback
+            ok = typeof_nodrop_ok(tbm, type_of, type_base, type_n, fcval, tv);
         miss += ok ? 0u : 1u;
         sid_t *dst = out + r * oc;
 #pragma unroll
@@ -1148,8 +775,4 @@ __global__ void k_expand_fn_map(const sid_t *__restrict__ tbl,
     if (miss)
         atomicAdd((unsigned long long *)&d_state[S_DONE],
                   (unsigned long long)miss);
-}
-
-__global__ void k_zero_words(uint64_t *p, int n) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
 }

@@ -27,13 +27,11 @@ struct fparams {
 __device__ __forceinline__ bool filter_keep(const fparams &P, int64_t r) {
     sid_t v = P.tbl[r * P.ncols + P.col];
     if (P.use_typeof) {
-        if (P.tbm)
-            // per-type bitmap: 1 bit/vid, whole map LLC-resident —
-            // exact (multi-type included), no probe fallback
-            return tbm_has(P.tbm, P.type_base, P.type_n, v);
-        uint64_t idx = (uint64_t)v - P.type_base;
-        uint16_t t = (idx < P.type_n) ? P.type_of[idx] : 0;
-        if (t != 0xFFFF) return (sid_t)t == P.cval;
+        // per-type bitmap (1 bit/vid, whole map LLC-resident, exact) or
+        // the dense index; multi-type falls through to the probe
+        const int tc = typeof_check(P.tbm, P.type_of, P.type_base, P.type_n,
+                                    P.cval, v);
+        if (tc != TC_MULTI) return tc == TC_YES;
     }
     if (P.probe_mode == PM_EQ) {
         // reversed functional map resolved host-side: the edge exists
@@ -187,11 +185,7 @@ __global__ void k_filter_tpr(fparams P, int verify_only, int batch,
     const int64_t nrows = (int64_t)d_state[S_NROWS];
     count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * filter_bytes_per_row(P));
     constexpr int K = 4;
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned int s_cnt;
-    __shared__ unsigned int s_wbase[SCAN_T / 64];
     const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
     const int ncols = P.ncols;
     const sid_t *__restrict__ tbl = P.tbl;
     const int64_t tile = (int64_t)blockDim.x * K;
@@ -199,7 +193,7 @@ __global__ void k_filter_tpr(fparams P, int verify_only, int batch,
     const int mode = batch ? filter_batch_mode(P) : FB_NONE;  // wave-uniform
 
     for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows; base += stride) {
-        bool keep[K];
+        uint32_t keep = 0;  // bit k: the thread's k-th row survives
         int64_t rr[K];
         if (mode != FB_NONE) {
             uint32_t in = 0;
@@ -209,19 +203,17 @@ __global__ void k_filter_tpr(fparams P, int verify_only, int batch,
                 in |= r < nrows ? 1u << k : 0u;
                 rr[k] = r < nrows ? r : base;  // base < nrows: a valid row
             }
-            const uint32_t m = filter_keep_batch<K>(P, mode, rr, in);
+            keep = filter_keep_batch<K>(P, mode, rr, in);
+            // a clamped row is never kept; past nrows for verify_only
 #pragma unroll
-            for (int k = 0; k < K; k++) {
-                keep[k] = (m >> k) & 1;
-                // a clamped row is never kept; past nrows for verify_only
+            for (int k = 0; k < K; k++)
                 rr[k] = ((in >> k) & 1) ? rr[k] : nrows;
-            }
         } else {
 #pragma unroll
             for (int k = 0; k < K; k++) {
                 const int64_t r = base + k * SCAN_T + threadIdx.x;
                 rr[k] = r;
-                keep[k] = r < nrows && filter_keep(P, r);
+                keep |= (r < nrows && filter_keep(P, r)) ? 1u << k : 0u;
             }
         }
         if (verify_only) {
@@ -232,35 +224,19 @@ __global__ void k_filter_tpr(fparams P, int verify_only, int batch,
             uint32_t miss = 0;
 #pragma unroll
             for (int k = 0; k < K; k++)
-                miss += (rr[k] < nrows && !keep[k]) ? 1u : 0u;
+                miss += (rr[k] < nrows && !((keep >> k) & 1)) ? 1u : 0u;
             if (miss)
                 atomicAdd((unsigned long long *)&d_state[S_DONE],
                           (unsigned long long)miss);
             continue;
         }
-        if (threadIdx.x == 0) s_cnt = 0;
-        __syncthreads();
+        // output <= input rows: no position can pass the capacity
         uint64_t mask[K];
-        uint32_t wtot = 0;
+        uint64_t wpos = tile_compact<K>(keep, d_state, mask);
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            mask[k] = __ballot(keep[k]);
-            wtot += (uint32_t)__popcll(mask[k]);
-        }
-        if (lane == 0) s_wbase[wid] = atomicAdd(&s_cnt, wtot);
-        __syncthreads();
-        if (threadIdx.x == 0)
-            s_base = s_cnt ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
-                                       (unsigned long long)s_cnt)
-                           : 0;
-        __syncthreads();
-        uint32_t wpos = s_wbase[wid];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            if (keep[k]) {
-                uint64_t pos = s_base + wpos +
-                               (uint32_t)__popcll(mask[k] &
-                                                  ((1ull << lane) - 1));
+            if ((keep >> k) & 1) {
+                const uint64_t pos = wpos + lanes_below(mask[k], lane);
                 sid_t *dst = out_tbl + (int64_t)pos * ncols;
                 const sid_t *srow = tbl + rr[k] * ncols;
                 for (int c = 0; c < ncols; c++) dst[c] = srow[c];
@@ -290,7 +266,7 @@ struct fprog_t {
     uint32_t bytes_per_row;  // 4 * distinct operand columns + 8 * ncols
 };
 
-// Same tile, ranks and cursor discipline as k_filter_tpr (5g(ii)); the
+// The tile and compaction of k_filter_tpr (tile_compact, 5g(ii)); the
 // keep decision is the program.  The program sits in the kernel-argument
 // segment and is walked with a wave-uniform index; the evaluation stack
 // of each of the thread's K rows is a bit-stack in one 32-bit register
@@ -304,24 +280,24 @@ __global__ void k_filter_expr(fprog_t P, uint64_t *__restrict__ d_state,
     const int64_t nrows = (int64_t)d_state[S_NROWS];
     count_bytes(d_stats, CAT_FILTER, (uint64_t)nrows * P.bytes_per_row);
     constexpr int K = 4;
-    __shared__ unsigned long long s_base;
-    __shared__ unsigned int s_cnt;
-    __shared__ unsigned int s_wbase[SCAN_T / 64];
     const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
     const int ncols = P.ncols;
     const sid_t *__restrict__ tbl = P.tbl;
     const int64_t tile = (int64_t)blockDim.x * K;
     const int64_t stride = (int64_t)gridDim.x * tile;
 
+    // (every [K] array below is indexed by fully unrolled loops only)
     for (int64_t base = (int64_t)blockIdx.x * tile; base < nrows; base += stride) {
-        const int64_t r0 = base + threadIdx.x;
-        const int64_t r1 = r0 + SCAN_T, r2 = r1 + SCAN_T, r3 = r2 + SCAN_T;
-        const bool in0 = r0 < nrows, in1 = r1 < nrows, in2 = r2 < nrows,
-                   in3 = r3 < nrows;
-        const sid_t *row0 = tbl + r0 * ncols, *row1 = tbl + r1 * ncols,
-                    *row2 = tbl + r2 * ncols, *row3 = tbl + r3 * ncols;
-        uint32_t st0 = 0, st1 = 0, st2 = 0, st3 = 0;
+        bool in[K];
+        const sid_t *row[K];
+        uint32_t st[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const int64_t r = base + k * SCAN_T + threadIdx.x;
+            in[k] = r < nrows;
+            row[k] = tbl + r * ncols;
+            st[k] = 0;
+        }
         for (int i = 0; i < P.n; i++) {
             const int op = P.node[i].op;
             if (op <= WK_F_BOUND) {
@@ -329,60 +305,47 @@ __global__ void k_filter_expr(fprog_t P, uint64_t *__restrict__ d_state,
                 const sid_t va = P.node[i].va;
                 const sid_t vb = (op == WK_F_BOUND) ? BLANK_ID : P.node[i].vb;
                 // rows past the end read nothing and are dropped below
-                const sid_t a0 = (ca >= 0 && in0) ? row0[ca] : va;
-                const sid_t a1 = (ca >= 0 && in1) ? row1[ca] : va;
-                const sid_t a2 = (ca >= 0 && in2) ? row2[ca] : va;
-                const sid_t a3 = (ca >= 0 && in3) ? row3[ca] : va;
-                const sid_t b0 = (cb >= 0 && in0) ? row0[cb] : vb;
-                const sid_t b1 = (cb >= 0 && in1) ? row1[cb] : vb;
-                const sid_t b2 = (cb >= 0 && in2) ? row2[cb] : vb;
-                const sid_t b3 = (cb >= 0 && in3) ? row3[cb] : vb;
+                sid_t a[K], b[K];
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    a[k] = (ca >= 0 && in[k]) ? row[k][ca] : va;
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    b[k] = (cb >= 0 && in[k]) ? row[k][cb] : vb;
                 // EQ pushes a == b; NE and BOUND (b = BLANK_ID) push a != b
                 const uint32_t inv = (op == WK_F_EQ) ? 0u : 1u;
-                st0 = (st0 << 1) | ((uint32_t)(a0 == b0) ^ inv);
-                st1 = (st1 << 1) | ((uint32_t)(a1 == b1) ^ inv);
-                st2 = (st2 << 1) | ((uint32_t)(a2 == b2) ^ inv);
-                st3 = (st3 << 1) | ((uint32_t)(a3 == b3) ^ inv);
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    st[k] = (st[k] << 1) | ((uint32_t)(a[k] == b[k]) ^ inv);
             } else if (op == WK_F_AND) {
-                st0 = (st0 >> 1) & (st0 | ~1u);
-                st1 = (st1 >> 1) & (st1 | ~1u);
-                st2 = (st2 >> 1) & (st2 | ~1u);
-                st3 = (st3 >> 1) & (st3 | ~1u);
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    st[k] = (st[k] >> 1) & (st[k] | ~1u);
             } else if (op == WK_F_OR) {
-                st0 = (st0 >> 1) | (st0 & 1u);
-                st1 = (st1 >> 1) | (st1 & 1u);
-                st2 = (st2 >> 1) | (st2 & 1u);
-                st3 = (st3 >> 1) | (st3 & 1u);
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    st[k] = (st[k] >> 1) | (st[k] & 1u);
             } else {  // WK_F_NOT
-                st0 ^= 1u; st1 ^= 1u; st2 ^= 1u; st3 ^= 1u;
+#pragma unroll
+                for (int k = 0; k < K; k++) st[k] ^= 1u;
             }
         }
-        const bool keep0 = in0 && (st0 & 1u), keep1 = in1 && (st1 & 1u),
-                   keep2 = in2 && (st2 & 1u), keep3 = in3 && (st3 & 1u);
-        if (threadIdx.x == 0) s_cnt = 0;
-        __syncthreads();
-        const uint64_t m0 = __ballot(keep0), m1 = __ballot(keep1),
-                       m2 = __ballot(keep2), m3 = __ballot(keep3);
-        const uint32_t c0 = (uint32_t)__popcll(m0), c1 = (uint32_t)__popcll(m1),
-                       c2 = (uint32_t)__popcll(m2), c3 = (uint32_t)__popcll(m3);
-        if (lane == 0) s_wbase[wid] = atomicAdd(&s_cnt, c0 + c1 + c2 + c3);
-        __syncthreads();
-        if (threadIdx.x == 0)
-            s_base = s_cnt ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
-                                       (unsigned long long)s_cnt)
-                           : 0;
-        __syncthreads();
-        const uint64_t below = (1ull << lane) - 1;
-        const uint64_t wpos = s_base + s_wbase[wid];
-        auto emit = [&](bool keep, uint64_t pos, const sid_t *srow) {
-            if (!keep) return;
-            sid_t *dst = out_tbl + (int64_t)pos * ncols;
-            for (int c = 0; c < ncols; c++) dst[c] = srow[c];
-        };
-        emit(keep0, wpos + (uint32_t)__popcll(m0 & below), row0);
-        emit(keep1, wpos + c0 + (uint32_t)__popcll(m1 & below), row1);
-        emit(keep2, wpos + c0 + c1 + (uint32_t)__popcll(m2 & below), row2);
-        emit(keep3, wpos + c0 + c1 + c2 + (uint32_t)__popcll(m3 & below), row3);
+        uint32_t keep = 0;
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            keep |= (in[k] && (st[k] & 1u)) ? 1u << k : 0u;
+        // output <= input rows: no position can pass the capacity
+        uint64_t mask[K];
+        uint64_t wpos = tile_compact<K>(keep, d_state, mask);
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            if ((keep >> k) & 1) {
+                const uint64_t pos = wpos + lanes_below(mask[k], lane);
+                sid_t *dst = out_tbl + (int64_t)pos * ncols;
+                for (int c = 0; c < ncols; c++) dst[c] = row[k][c];
+            }
+            wpos += (uint32_t)__popcll(mask[k]);
+        }
     }
 }
 
@@ -526,7 +489,6 @@ __global__ void k_expand_opt(const vertex_t *__restrict__ verts,
     // replaces the round-1 per-row cursors — a single cursor word
     // saturates at ~88 atomics/us (microarch row `dequeue`)
     __shared__ unsigned long long s_base;
-    __shared__ uint64_t sh[SCAN_T];
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < nrows;
          base += stride) {
@@ -549,16 +511,10 @@ __global__ void k_expand_opt(const vertex_t *__restrict__ verts,
             // (sparql.hpp:328-334, 352-356)
             emit = (!m || v == BLANK_ID || esz == 0) ? 1 : esz;
         }
-        sh[threadIdx.x] = emit;
-        __syncthreads();
-        for (int ofs = 1; ofs < SCAN_T; ofs <<= 1) {
-            uint64_t x = (threadIdx.x >= (unsigned)ofs) ? sh[threadIdx.x - ofs] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += x;
-            __syncthreads();
-        }
-        const uint64_t my_end = sh[threadIdx.x];
-        const uint64_t block_total = sh[SCAN_T - 1];
+        // (the scan's barriers also separate the previous tile's reads of
+        // s_base from this tile's write: no barrier at the loop's end)
+        uint64_t block_total;
+        const uint64_t my_end = block_ladder_scan(emit, &block_total);
         if (threadIdx.x == SCAN_T - 1)
             s_base = block_total
                          ? atomicAdd((unsigned long long *)&d_state[S_TOTAL],
@@ -583,6 +539,5 @@ __global__ void k_expand_opt(const vertex_t *__restrict__ verts,
                 }
             }
         }
-        __syncthreads();
     }
 }
